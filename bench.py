@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the SMART-Vocoder inference path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 16] [--frames 512]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 16] [--frames 512] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +10,10 @@ iitp_base, batch 16 x 512 frames per GPU, 22.05 kHz), inputs resident in HBM.  M
 (whole job).  Weak scaling: every rank runs its own 16x512 shard; rank 0 owns the job's batch
 (scattered over RCCL before the timed region) and receives all waveforms (gather inside the timed region).
 Prints ONE JSON line on rank 0.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step returned as DIR/<name>.npy (float32):
+at N=1 every output of `infer` (o, x_mask, z, z_p, m_p, logs_p), at N>1 the gathered waveform o.  Inputs and weights are
+seeded, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -214,6 +218,32 @@ def live_hbm_traffic(B, T, timeout_s=150):
         shutil.rmtree(base, ignore_errors=True)
 
 
+DUMP_BYTES = 64_000_000              # --dump-outputs: the whole dump stays under 64 MB
+DUMP_SEED = 1001
+
+
+def dump_outputs(d, arrays):
+    """Write every array of `arrays` ({name: tensor}) as d/<name>.npy in float32.  If together they exceed DUMP_BYTES, each
+    keeps the same share of its elements: a seeded sample, flattened, in increasing index order (the same shapes pick the same
+    positions in every run).  Returns {name: description} for the JSON line."""
+    import zlib
+    os.makedirs(d, exist_ok=True)
+    total = sum(t.numel() for t in arrays.values())
+    budget = (DUMP_BYTES - 4096 * len(arrays)) // 4                 # float32 elements, with room for the .npy headers
+    info = {}
+    for name, t in arrays.items():
+        a = t.detach().to(device="cpu", dtype=torch.float32).contiguous().numpy()
+        rec = {"shape": list(a.shape), "dtype": "float32", "sampled": total > budget}
+        if total > budget:
+            k = budget * a.size // total
+            rng = np.random.default_rng([DUMP_SEED, zlib.crc32(name.encode())])
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, size=k, replace=False, shuffle=False))]
+            rec.update(elements=int(k), sample=f"seeded ({DUMP_SEED}, crc32 of the name) choice of {k} of {t.numel()} flat indices, ascending")
+        np.save(os.path.join(d, name + ".npy"), a)
+        info[name] = rec
+    return info
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -225,7 +255,10 @@ def main():
     ap.add_argument("--no-pmc", action="store_true", help="skip the live HBM-traffic passes (rocprofv3 --pmc child runs of this script)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the C1 / C3 / C5 timings after the timed region")
     ap.add_argument("--allow-no-collective", action="store_true", help="N>1: do not fail when neither gather nor all_gather works")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float32, <= 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import cases
     from cases import sw
@@ -307,19 +340,23 @@ def main():
         return o
 
     marks = []                                     # N>1: (before infer, after infer, after gather) events of every timed step, on the launch stream
+    last = []                                      # infer's outputs of the last timed step (--dump-outputs)
 
-    def step(timed=False):
+    def step(timed=False, keep=False):
         if timed and use_dist:
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
             ev[0].record()
-            o = net.infer(mel, ln, noise_scale=0.667, eps=eps)[0]
+            res = net.infer(mel, ln, noise_scale=0.667, eps=eps)
             ev[1].record()
-            r = collect(o)
+            r = collect(res[0])
             ev[2].record()
             marks.append(ev)
-            return r
-        o = net.infer(mel, ln, noise_scale=0.667, eps=eps)[0]
-        return collect(o)
+        else:
+            res = net.infer(mel, ln, noise_scale=0.667, eps=eps)
+            r = collect(res[0])
+        if keep:
+            last[:] = [res]
+        return r
 
     if use_dist:   # choose a collective that works on this node before any timing
         with torch.no_grad():
@@ -354,8 +391,8 @@ def main():
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
         ev0.record()                     # the HIP kernels are enqueued on torch's current stream
-        for _ in range(args.steps):
-            out = step(timed=True)
+        for i in range(args.steps):
+            out = step(timed=True, keep=i == args.steps - 1)
         ev1.record()
         torch.cuda.synchronize()
         if use_dist:
@@ -366,6 +403,13 @@ def main():
         # not printed for such a run (include/svoc.h svoc_check_async_error; needs no synchronisation beyond the one above)
         _native.check_async_error()
     gpu_ms = ev0.elapsed_time(ev1)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: infer's outputs (N=1) or the gathered waveforms (N>1)
+        o_last, x_mask, (z, z_p, m_p, logs_p) = last[0]
+        arrays = {"o": out} if use_dist else {"o": o_last, "x_mask": x_mask, "z": z, "z_p": z_p, "m_p": m_p, "logs_p": logs_p}
+        dumped = dump_outputs(args.dump_outputs, arrays)
+    last.clear()
     stats = _native.stats_get()
     scatter_ms = None
     if use_dist and scatter_ok:
@@ -453,6 +497,8 @@ def main():
             "real_time_factor": value / SAMPLE_RATE / world,
             "samples_per_s_per_gpu": value / world,
         }
+        if dumped is not None:
+            res["dump_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "arrays": dumped}
         if per_rank is not None:
             res["per_rank"] = per_rank
             res["step_ms_min_over_ranks"] = min(per_rank["step_wall_ms"])

@@ -10,6 +10,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
@@ -179,12 +180,14 @@ def test_two_processes_one_gpu_alternating_inputs():
         assert p.returncode == 0 and o.strip().endswith("OK"), o[-2000:]
 
 
-def test_bench_single_gpu_line_schema():
+def test_bench_single_gpu_line_schema(tmp_path):
     """bench.py at N=1 on the timed configuration (16 x 512, 2 steps, no CPU leg): ONE JSON line with the contract's keys, the
     roofline block (`frac` = executed multiply-adds over the peak, bounded by 1; `frac_direct_form`, which the Winograd kernels may
     push above 1), the library's launch statistics, the HBM traffic of the step and the hardware's MFMA count of the default plan
-    (live PMC passes; the count must agree with the library's bookkeeping to 1.5 %), and the C1 / C3 / C5 timings."""
-    cmd = [sys.executable, os.path.join(cases.ROOT, "bench.py"), "--steps", "2", "--warmup", "2", "--no-cpu-baseline"]
+    (live PMC passes; the count must agree with the library's bookkeeping to 1.5 %), and the C1 / C3 / C5 timings.  --dump-outputs
+    writes every output of the last timed step's `infer`, whole, as float32."""
+    cmd = [sys.executable, os.path.join(cases.ROOT, "bench.py"), "--steps", "2", "--warmup", "2", "--no-cpu-baseline",
+           "--dump-outputs", str(tmp_path / "dump")]
     r = subprocess.run(cmd, env=dict(os.environ), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -210,6 +213,13 @@ def test_bench_single_gpu_line_schema():
     # HBM traffic: live rocprofv3 --pmc child runs (or, should the profiler fail on the box, this round's committed passes)
     assert rf["traffic"] is not None and rf["traffic_source"].startswith(("LIVE", "OFFLINE")), rf
     assert 2e10 < rf["traffic_bytes_per_step"] < 8e10, rf["traffic_bytes_per_step"]
+    dump = j["dump_outputs"]["arrays"]
+    shapes = {"o": (16, 1, 512 * 256), "x_mask": (16, 1, 512), "z": (16, 192, 512), "z_p": (16, 192, 512), "m_p": (16, 192, 512), "logs_p": (16, 192, 512)}
+    assert sorted(os.listdir(tmp_path / "dump")) == sorted(f"{n}.npy" for n in shapes) and not any(v["sampled"] for v in dump.values()), dump
+    for n, sh in shapes.items():
+        a = np.load(tmp_path / "dump" / f"{n}.npy")
+        assert a.dtype == np.float32 and a.shape == sh and np.isfinite(a).all(), n
+    assert sum(os.path.getsize(tmp_path / "dump" / f) for f in os.listdir(tmp_path / "dump")) <= 64e6
 
 
 _RCCL_WORLD1 = r'''
