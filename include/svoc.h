@@ -183,6 +183,22 @@ int svoc_generator_forward(svoc_generator* h, void* stream, const float* x, int 
                            const float* in_mask, int64_t in_mask_bs, const float* g, float* out, int B, int T);
 void svoc_generator_destroy(svoc_generator* h);
 
+/* ---- decoder precision (ABI 7) ----------------------------------------------
+ * SVOC_PREC_F32 (default): every path above, unchanged.  SVOC_PREC_F16: every ResBlock convolution of the decoder (ResBlock1
+ * convs1.* / convs2.*, ResBlock2 convs.*, all MRF stages) runs on a direct-form fp16 MFMA kernel (csrc/conv_f16.hip), and:
+ *   - the activation leaky_relu(x, 0.1) is rounded to fp16 with round-to-nearest-even;
+ *   - the weight-norm-folded weight is rounded to fp16 the same way, once, when the fp16 images are built;
+ *   - the products are summed in fp32 (MFMA f32 accumulators);
+ *   - bias, residual add, the MRF sum over the chains and the / n_kernels stay fp32, and so do the activations in memory;
+ *   - the encoder, the flow, conv_pre (+ cond), the upsamplers and conv_post + tanh run exactly as in fp32 mode (the first MRF
+ *     stage's input is bit-identical between the modes).
+ * No clamping: an activation beyond the fp16 range (|x| > 65504) becomes +-inf, as a cast would make it.
+ * The first switch of a handle to SVOC_PREC_F16 builds the fp16 weight images and blocks, like *_create; a handle that stays in
+ * fp32 allocates nothing for them.  Captured plans (svoc_synth_infer) are keyed by the mode and never replay in the other one.
+ * Returns the previous mode, or SVOC_ERR_INVALID_ARG for an unknown mode.  Replaces nothing in the reference (one precision). */
+enum { SVOC_PREC_F32 = 0, SVOC_PREC_F16 = 1 };
+int svoc_generator_set_decoder_precision(svoc_generator* h, int mode);
+
 /* ---- models.SynthesizerTrn.infer (models.py:266-339) ---------------------- */
 typedef struct svoc_synth svoc_synth;
 typedef struct svoc_synth_config {
@@ -214,6 +230,8 @@ int64_t svoc_synth_workspace_bytes(svoc_synth* h, int B, int T);
  * SVOC_GRAPH_MAX_FRAMES) are replayed from a hipGraph captured on their second call (SVOC_GRAPH=0 disables). */
 int svoc_synth_reserve(svoc_synth* h, int B, int T);
 int svoc_synth_hop(svoc_synth* h);         /* prod(upsample_rates) */
+/* the decoder's precision, SVOC_PREC_F32 or SVOC_PREC_F16 (see svoc_generator_set_decoder_precision above); returns the previous mode */
+int svoc_synth_set_decoder_precision(svoc_synth* h, int mode);
 /* Captured-plan bookkeeping of a handle: out5 = {live plans, captures so far, plans evicted, evictions that had to wait
  * (hipEventSynchronize on the evicted plan's own completion event), plans retired but still executing}.  A shape earns
  * a plan on its SVOC_GRAPH_MIN_SEEN-th call (default 2; first sights only bump a counter); at most 32 plans live, the
@@ -327,6 +345,12 @@ int svoc_conv1d(void* stream, const float* x, const float* weight_v, const float
 int svoc_conv1d_winograd(void* stream, const float* x, const float* weight_v, const float* weight_g, const float* bias,
                          const float* residual, float* y, int B, int Cin, int Cout, int L, int kernel_size, int dilation,
                          float pre_slope);
+/* The same operation in the decoder's fp16 mode (csrc/conv_f16.hip; numerics: svoc_generator_set_decoder_precision above): any channel
+ * counts (tiles of 32 rows / channels, zero-padded), odd kernel_size, any L and B.  Blocks until the result is ready.  SVOC_ERR_UNSUPPORTED
+ * for an even kernel_size or a window of (kernel_size - 1) * dilation beyond the kernel's LDS. */
+int svoc_conv1d_f16(void* stream, const float* x, const float* weight_v, const float* weight_g, const float* bias,
+                    const float* residual, float* y, int B, int Cin, int Cout, int L, int kernel_size, int dilation,
+                    float pre_slope);
 /* F.leaky_relu -> weight-normed ConvTranspose1d(k, stride, padding=(k-stride)//2) (models.py:125-127, 147-148):
  * x [B,Cin,L], weight_v [Cin,Cout,k], weight_g [Cin,1,1] or NULL, y [B,Cout,L*stride].  k = 2 * stride with stride 8 or 2,
  * Cin % 64 == 0, Cout * stride % 64 == 0, L % 4 == 0 and at least half as many tiles as CUs: Winograd F(4,2) over the polyphase

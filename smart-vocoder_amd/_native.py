@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SVOC_LIB selects another build of the same library (A/B comparisons of kernel variants on one GPU box)
 LIB_PATH = os.environ.get("SVOC_LIB") or os.path.join(_HERE, "csrc", "libsvoc_hip.so")
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 _lib = None
 
 
@@ -77,6 +77,7 @@ SIGNATURES = {
     "svoc_generator_create": (_I, [C.POINTER(_P), C.POINTER(svoc_generator_config), *_TAB, C.c_char_p]),
     "svoc_generator_forward": (_I, [_P, _P, _P, _I, _L, _P, _L, _P, _P, _I, _I]),
     "svoc_generator_destroy": (None, [_P]),
+    "svoc_generator_set_decoder_precision": (_I, [_P, _I]),
     "svoc_synth_create": (_I, [C.POINTER(_P), C.POINTER(svoc_synth_config), *_TAB]),
     "svoc_synth_infer": (_I, [_P, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P, _I, _I]),
     "svoc_synth_workspace_bytes": (_L, [_P, _I, _I]),
@@ -84,6 +85,7 @@ SIGNATURES = {
     "svoc_synth_hop": (_I, [_P]),
     "svoc_synth_plan_stats": (_I, [_P, C.POINTER(_L)]),
     "svoc_synth_destroy": (None, [_P]),
+    "svoc_synth_set_decoder_precision": (_I, [_P, _I]),
     "svoc_posterior_create": (_I, [C.POINTER(_P), _I, _I, _I, _I, _I, _I, _I, *_TAB, C.c_char_p]),
     "svoc_posterior_forward": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I]),
     "svoc_posterior_destroy": (None, [_P]),
@@ -112,6 +114,7 @@ SIGNATURES = {
     "svoc_fold_weight_norm": (_I, [_P, _P, _P, _P, _L, _L]),
     "svoc_conv1d": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F]),
     "svoc_conv1d_winograd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F]),
+    "svoc_conv1d_f16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F]),
     "svoc_conv_transpose1d": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F]),
 }
 

@@ -242,6 +242,9 @@ struct ResBlock {
   int kind = 1, C = 0, K = 0, ND = 0;
   std::vector<std::unique_ptr<PackedConv>> c1, c2;
   std::vector<std::unique_ptr<PackedWino>> w1, w2;   // Winograd form of the undilated convolutions (null where not applicable)
+  // fp16 images of c1 / c2 (conv_f16.hip), built the first time the owning decoder is switched to SVOC_PREC_F16; f16: run() issues them
+  std::vector<std::unique_ptr<PackedConvF16>> h1, h2;
+  bool f16 = false;
   DevBuf ws;
 
   int create(int kind_, int channels, int k, const int* dil, int nd, const TensorTable& tab, const std::string& prefix, hipStream_t st) {
@@ -271,10 +274,60 @@ struct ResBlock {
     return SVOC_OK;
   }
 
+  int build_f16(hipStream_t st) {
+    if (!h1.empty()) return SVOC_OK;
+    std::vector<std::unique_ptr<PackedConvF16>> n1, n2;
+    for (int i = 0; i < ND; ++i) {
+      n1.emplace_back(new PackedConvF16());
+      SVOC_TRY(pack_conv_f16(*n1.back(), *c1[i], st));
+      if (kind == 1) {
+        n2.emplace_back(new PackedConvF16());
+        SVOC_TRY(pack_conv_f16(*n2.back(), *c2[i], st));
+      }
+    }
+    h1 = std::move(n1); h2 = std::move(n2);
+    return SVOC_OK;
+  }
+
+  // fp16 mode: every convolution on conv_f16.hip, one launch each.  ResBlock1: c1 (dilated) -> scratch, c2 + x -> next (in place is
+  // safe: c2 reads scratch, the residual elementwise); ResBlock2: the convolution reads `cur` with halos, so it never writes in place.
+  int run_f16(hipStream_t st, const float* x, long long x_bs, int x_ld, float* A, float* Bf, long long bs, int ld, const ResSink& sink,
+              int B, int L, hipEvent_t wait_before_last, hipEvent_t record_after_last) {
+    if (h1.size() != (size_t)ND) SVOC_FAIL(SVOC_ERR_INVALID_ARG, "ResBlock: fp16 mode without fp16 weight images");
+    const float* cur = x; long long cur_bs = x_bs; int cur_ld = x_ld;
+    for (int i = 0; i < ND; ++i) {
+      const bool last = i == ND - 1;
+      const float* cin = cur; long long cin_bs = cur_bs; int cin_ld = cur_ld;
+      float* nxt;
+      if (kind == 1) {
+        float* scratch = (cur == A) ? Bf : A;
+        EpiOut o{}; set_out(o, scratch, bs, ld, C);
+        SVOC_TRY(launch_conv_f16(*h1[i], cur, cur_bs, cur_ld, 0.1f, o, B, L, st));
+        cin = scratch; cin_bs = bs; cin_ld = ld;
+        nxt = (cur == A || cur == Bf) ? const_cast<float*>(cur) : Bf;
+      } else {
+        nxt = (cur == A) ? Bf : A;
+      }
+      EpiOut o{};
+      if (!last) set_out(o, nxt, bs, ld, C, F_RES);
+      else { set_out(o, sink.y, sink.bs, sink.ld, C, F_RES | sink.flags); o.div = sink.div; }
+      set_res(o, cur, cur_bs, cur_ld);
+      if (last && wait_before_last) SVOC_HIP(hipStreamWaitEvent(st, wait_before_last, 0));
+      SVOC_TRY(launch_conv_f16(kind == 1 ? *h2[i] : *h1[i], cin, cin_bs, cin_ld, 0.1f, o, B, L, st));
+      if (last && record_after_last) SVOC_HIP(hipEventRecord(record_after_last, st));
+      cur = nxt; cur_bs = bs; cur_ld = ld;
+    }
+    return SVOC_OK;
+  }
+
   // x read-only [B][C][x_ld]; A, Bf scratch [B][C][ld]; the block's result goes to `sink`
   int run(hipStream_t st, const float* x, long long x_bs, int x_ld, const float* mask, long long mask_bs, float* A,
           float* Bf, long long bs, int ld, const ResSink& sink, int B, int L, hipEvent_t wait_before_last = nullptr,
           hipEvent_t record_after_last = nullptr) {
+    if (f16) {
+      if (mask) SVOC_FAIL(SVOC_ERR_UNSUPPORTED, "ResBlock: the fp16 mode takes no input mask");
+      return run_f16(st, x, x_bs, x_ld, A, Bf, bs, ld, sink, B, L, wait_before_last, record_after_last);
+    }
     const float* cur = x; long long cur_bs = x_bs; int cur_ld = x_ld;
     for (int i = 0; i < ND; ++i) {
       const bool last = i == ND - 1;
@@ -483,6 +536,7 @@ struct Generator {
   std::vector<hipEvent_t> chain_done;
   hipEvent_t ev_fork = nullptr;
   bool use_streams = true;
+  int precision = SVOC_PREC_F32;                           // SVOC_PREC_F16: every ResBlock convolution on conv_f16.hip (set_precision)
   ~Generator() {
     for (auto s : chain_st) if (s) (void)hipStreamDestroy(s);
     for (auto e : chain_done) if (e) (void)hipEventDestroy(e);
@@ -543,6 +597,17 @@ struct Generator {
     SVOC_HIP(hipMemcpyAsync(conv_post_w.p, pw->data, (size_t)ch * 7 * sizeof(float), hipMemcpyDeviceToDevice, st));
     SVOC_HIP(hipStreamSynchronize(st));
     return SVOC_OK;
+  }
+
+  // Switches the ResBlock convolutions between the fp32 kernels and conv_f16.hip.  The fp16 images are built on the first switch to
+  // SVOC_PREC_F16 (blocks, like create); an fp32-only handle never allocates them.  Returns the previous mode.
+  int set_precision(int mode, hipStream_t st) {
+    if (mode != SVOC_PREC_F32 && mode != SVOC_PREC_F16) SVOC_FAIL(SVOC_ERR_INVALID_ARG, "decoder precision %d: expected SVOC_PREC_F32 or SVOC_PREC_F16", mode);
+    const int prev = precision;
+    if (mode == SVOC_PREC_F16) for (auto& rb : rbs) SVOC_TRY(rb->build_f16(st));
+    for (auto& rb : rbs) rb->f16 = mode == SVOC_PREC_F16;
+    precision = mode;
+    return prev;
   }
 
   size_t stage_floats(int T) const {   // largest [C_i][stage_ld(L_i)] over conv_pre output and all stages
@@ -812,7 +877,8 @@ struct Generator {
         if (mtl == 1) tiles = (long long)cfg.n_kernels * variant_batch(B) * ((Lo + 511) / 512);    // F(4,3), one row tile: 512 outputs per workgroup tile
         small_stage = on && (tiles < mrf_min_tiles() || (mtl == 1 && (Lo & 3)));
       }
-      if (use_streams && !small_stage && mrf_grouped(i, cho)) {
+      // fp16 mode: the chains always run on the stream plan below, one conv_f16.hip launch per convolution
+      if (use_streams && !small_stage && precision == SVOC_PREC_F32 && mrf_grouped(i, cho)) {
         // MRF with the chains' step-i convolutions grouped into single launches (conv_group_kernel)
         SVOC_TRY(run_mrf_grouped(st, i, X, XS, bufs, bs, ldo, cho, B, Lo));
         r ^= 1;
@@ -1052,8 +1118,10 @@ struct Synth {
   struct PlanKey {
     int B = 0, T = 0, Td = 0; float noise = 0; bool has_eps = false, want_zp = false;
     int vb = 0;                         // variant_batch(B) at capture: the kernel variants are frozen into the graph
+    int prec = SVOC_PREC_F32;           // the decoder's precision at capture: a plan never replays in the other mode
     bool operator==(const PlanKey& o) const {
-      return B == o.B && T == o.T && Td == o.Td && noise == o.noise && has_eps == o.has_eps && want_zp == o.want_zp && vb == o.vb;
+      return B == o.B && T == o.T && Td == o.Td && noise == o.noise && has_eps == o.has_eps && want_zp == o.want_zp && vb == o.vb &&
+             prec == o.prec;
     }
   };
   struct Plan {
@@ -1205,6 +1273,7 @@ struct Synth {
     const bool want_zp = z_p != nullptr;
     PlanKey key; key.B = B; key.T = T; key.Td = Td; key.noise = noise_scale; key.has_eps = eps != nullptr; key.want_zp = want_zp;
     key.vb = variant_batch(B);
+    key.prec = dec.precision;
     if (Plan* pl = plan_for(key, st)) {
       Stage sp;
       SVOC_TRY(stage_ptrs(sp));
@@ -1348,6 +1417,12 @@ int svoc_generator_forward(svoc_generator* h, void* stream, const float* x, int 
   return h->m.forward(as_stream(stream), x, x_ld, x_bs, in_mask, in_mask_bs, g, out, B, T);
   SVOC_GUARD_END
 }
+int svoc_generator_set_decoder_precision(svoc_generator* h, int mode) {
+  if (!h) SVOC_FAIL(SVOC_ERR_INVALID_ARG, "svoc_generator_set_decoder_precision: null handle");
+  SVOC_GUARD_BEGIN
+  return h->m.set_precision(mode, nullptr);
+  SVOC_GUARD_END
+}
 void svoc_generator_destroy(svoc_generator* h) { svoc::destroy_handle(h); }
 
 int svoc_synth_create(svoc_synth** out, const svoc_synth_config* cfg, const svoc_tensor* tensors, int n_tensors) {
@@ -1370,6 +1445,12 @@ int svoc_synth_infer(svoc_synth* h, void* stream, const float* mel, const int64_
   SVOC_GUARD_END
 }
 int64_t svoc_synth_workspace_bytes(svoc_synth* h, int B, int T) { return h ? h->m.workspace_bytes(B, T) : 0; }
+int svoc_synth_set_decoder_precision(svoc_synth* h, int mode) {
+  if (!h) SVOC_FAIL(SVOC_ERR_INVALID_ARG, "svoc_synth_set_decoder_precision: null handle");
+  SVOC_GUARD_BEGIN
+  return h->m.dec.set_precision(mode, nullptr);
+  SVOC_GUARD_END
+}
 int svoc_synth_reserve(svoc_synth* h, int B, int T) {
   if (!h || B <= 0 || T <= 0) SVOC_FAIL(SVOC_ERR_INVALID_ARG, "svoc_synth_reserve: bad arguments");
   SVOC_GUARD_BEGIN
@@ -1512,6 +1593,26 @@ int svoc_conv1d(void* stream, const float* x, const float* weight_v, const float
   set_out(a.out[0], y, (long long)Cout * L, L, Cout, residual ? (unsigned)F_RES : 0u);
   if (residual) set_res(a.out[0], residual, (long long)Cout * L, L);
   SVOC_TRY(launch_conv(pc, a, B, st));
+  SVOC_HIP(hipStreamSynchronize(st));   // packed weights are freed on return
+  return SVOC_OK;
+  SVOC_GUARD_END
+}
+int svoc_conv1d_f16(void* stream, const float* x, const float* weight_v, const float* weight_g, const float* bias, const float* residual,
+                    float* y, int B, int Cin, int Cout, int L, int kernel_size, int dilation, float pre_slope) {
+  if (!x || !weight_v || !y || B <= 0 || L <= 0) SVOC_FAIL(SVOC_ERR_INVALID_ARG, "svoc_conv1d_f16: bad arguments");
+  if (!conv_f16_supported(Cin, Cout, kernel_size, dilation))
+    SVOC_FAIL(SVOC_ERR_UNSUPPORTED, "svoc_conv1d_f16: odd kernel size and a window of (k - 1) * dilation that fits the LDS");
+  SVOC_GUARD_BEGIN
+  hipStream_t st = as_stream(stream);
+  PackedConv pc;
+  PackSpec sp{}; sp.Cin = Cin; sp.Cout = Cout; sp.K = kernel_size; sp.dil = dilation;
+  SVOC_TRY(pack_conv(pc, sp, weight_v, weight_g, bias, st));
+  PackedConvF16 pf;
+  SVOC_TRY(pack_conv_f16(pf, pc, st));
+  EpiOut o{};
+  set_out(o, y, (long long)Cout * L, L, Cout, residual ? (unsigned)F_RES : 0u);
+  if (residual) set_res(o, residual, (long long)Cout * L, L);
+  SVOC_TRY(launch_conv_f16(pf, x, (long long)Cin * L, L, pre_slope, o, B, L, st));
   SVOC_HIP(hipStreamSynchronize(st));   // packed weights are freed on return
   return SVOC_OK;
   SVOC_GUARD_END

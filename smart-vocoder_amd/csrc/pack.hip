@@ -10,6 +10,8 @@
 //   - the tile-pair interleave of two-half convolutions (WN gate, proj, coupling stats),
 //   - modules.Flip (modules.py:270-277) as channel permutations,
 //   - the polyphase split of ConvTranspose1d: virtual row o*s + r uses taps r, r+s, ...
+// This layout has a second reader: conv_f16.hip's pack_f16_kernel decodes it (plain same-padded convolutions) into the fp16
+// A-fragment image of the decoder's fp16 mode.  Change the two together; tests/test_gpu_fp16_decoder.py checks the result.
 #include "svoc_internal.h"
 
 namespace svoc {

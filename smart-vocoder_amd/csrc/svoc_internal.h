@@ -228,6 +228,20 @@ int pack_convt_wino_named(PackedCtWino& pw, int Cin, int Cout, int K, int stride
 int launch_convt_wino(const PackedCtWino& pw, const float* x, long long x_bs, int x_ld, float pre_slope, float* y, long long y_bs,
                       int y_ld, int B, int Lin, hipStream_t st);
 
+// conv_f16.hip: the opt-in fp16 form of a ResBlock convolution (SVOC_PREC_F16): direct form on v_mfma_f32_32x32x16_f16, activation and weight
+// rounded to fp16 (RNE), fp32 accumulation and epilogue
+struct PackedConvF16 {
+  DevBuf wp;                      // [ceil(Cout/32)][K][CinP/16][lane][8] fp16 A fragments (zero padding rows / channels)
+  const float* bias = nullptr;    // the fp32 PackedConv's bias (owned there)
+  int Cin = 0, Cout = 0, K = 0, dil = 1, pad = 0;
+  double flops_per_col = 0;
+};
+bool conv_f16_supported(int Cin, int Cout, int K, int dil);
+int pack_conv_f16(PackedConvF16& pf, const PackedConv& pc, hipStream_t st);     // blocks until the image is built
+// `out`: flags within F_RES | F_ACC | F_DIV; x [B][Cin][x_ld], columns outside [0, L) read as zero
+int launch_conv_f16(const PackedConvF16& pf, const float* x, long long x_bs, int x_ld, float slope, const EpiOut& out, int B, int L,
+                    hipStream_t st);
+
 // resblock_fused.hip: one ResBlock1 iteration (c1 -> lrelu -> c2 -> + x) in one kernel; returns 1 when not eligible
 void set_debug_stamp_buffer(long long* p);
 long long* debug_stamp_buffer();   // misc_kernels.hip: device buffer for per-workgroup cycle stamps, or nullptr

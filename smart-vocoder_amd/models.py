@@ -150,6 +150,28 @@ class PosteriorEncoder(_HipModule):
         return z, m, logs, x_mask
 
 
+# decoder_precision= of infer / infer_chunked / stream / Generator.forward (extension): "fp32" (default, the reference's numerics) or
+# "fp16" (every ResBlock convolution on the fp16 MFMA kernel; contract in include/svoc.h and INTEGRATION.md)
+_DECODER_PRECISIONS = {"fp32": 0, "fp16": 1}
+
+
+def _decoder_precision(value):
+    """The library's mode for a decoder_precision= value; anything but "fp32" / "fp16" raises ValueError (before any device work)."""
+    if not isinstance(value, str) or value not in _DECODER_PRECISIONS:
+        raise ValueError(f"decoder_precision must be 'fp32' or 'fp16', got {value!r}")
+    return _DECODER_PRECISIONS[value]
+
+
+def _set_decoder_precision(module, h, setter, mode):
+    """Switches the module's handle `h` to `mode` when it is in the other one.  The mode lives on the Handle object: a handle rebuilt by
+    _native() (weights changed) starts in fp32 and is switched again here."""
+    if module._nh.__dict__.get("decoder_precision", 0) != mode:
+        rc = setter(h, mode)
+        if rc < 0:
+            N.check(rc)
+        module._nh.__dict__["decoder_precision"] = mode
+
+
 def _gen_config(initial_channel, resblock, rks, rds, ur, uic, uks, gin):
     c = N.svoc_generator_config()
     if len(rks) > 8 or len(ur) > 8 or any(len(d) > 8 for d in rds):
@@ -208,7 +230,8 @@ class Generator(_HipModule):
         cfg = self._config()
         N.check(N.lib().svoc_generator_create(h.out(), cfg, tab.arr, tab.n, b""))
 
-    def forward(self, x, g=None):
+    def forward(self, x, g=None, *, decoder_precision="fp32"):
+        mode = _decoder_precision(decoder_precision)
         x = N.f32(x)
         B, Cc, T = x.shape
         _check_channels("Generator", Cc, self._cfg_args[0])
@@ -219,7 +242,9 @@ class Generator(_HipModule):
         out = torch.empty(B, 1, T * self.hop, dtype=torch.float32, device=x.device)
         _same_device(x, g)
         with torch.cuda.device(x.device):
-            N.check(N.lib().svoc_generator_forward(self._native(), N.stream_ptr(x.device), N.ptr(x), T, Cc * T, None, 0,
+            h = self._native()
+            _set_decoder_precision(self, h, N.lib().svoc_generator_set_decoder_precision, mode)
+            N.check(N.lib().svoc_generator_forward(h, N.stream_ptr(x.device), N.ptr(x), T, Cc * T, None, 0,
                                                    N.ptr(g), N.ptr(out), B, T))
         return out
 
@@ -309,7 +334,8 @@ class SynthesizerTrn(_HipModule):
     def forward(self, x, x_lengths, y, y_lengths, sid=None):
         raise NotImplementedError("training forward is outside the MI355X inference path; use infer()")
 
-    def infer(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., max_len=None, eps=None):
+    def infer(self, x, x_lengths, sid=None, noise_scale=1, length_scale=1, noise_scale_w=1., max_len=None, eps=None, *,
+              decoder_precision="fp32"):
         """mel [B,80,T], lengths [B] -> (o [B,1,min(T,max_len)*hop], x_mask [B,1,T], (z, z_p, m_p, logs_p)).
 
         As in the reference, speaker conditioning is off (g=None, models.py:332) and sid/length_scale/noise_scale_w
@@ -322,7 +348,12 @@ class SynthesizerTrn(_HipModule):
         workspace for it first (``svoc_synth_reserve``: a no-op unless one has to grow; then one device synchronisation +
         reallocation, BEFORE anything of this call is enqueued, never in the middle of it).  Call ``reserve(batch, frames)``
         once with the largest shape to keep every later ``infer`` free of allocations and synchronisations.
+
+        ``decoder_precision`` (extension, keyword only): ``"fp32"`` (default) or ``"fp16"``, which runs every ResBlock convolution
+        of the decoder on fp16 MFMA (activations and weights rounded to fp16, fp32 sums).  The first fp16 call
+        builds the fp16 weight images and blocks.
         """
+        mode = _decoder_precision(decoder_precision)
         x = N.f32(x)
         if x.dim() != 3 or x.shape[1] != 80:
             raise ValueError(f"expected mel [B, 80, T], got {tuple(x.shape)}")
@@ -352,6 +383,7 @@ class SynthesizerTrn(_HipModule):
                 if len(seen) >= 4096:
                     seen.clear()
                 seen.add((B, T))
+            _set_decoder_precision(self, h, N.lib().svoc_synth_set_decoder_precision, mode)
             N.check(N.lib().svoc_synth_infer(h, N.stream_ptr(dev), N.ptr(x), N.ptr(ln), N.ptr(eps),
                                              float(noise_scale), Td, N.ptr(o), N.ptr(x_mask), N.ptr(z), N.ptr(z_p),
                                              N.ptr(m_p), N.ptr(logs_p), B, T))
@@ -374,14 +406,15 @@ class SynthesizerTrn(_HipModule):
     # (decoder_receptive_frames; iitp_base: 3 + 1 + 60/8 + 60/64 + 60/128 + 60/256 + taps -> 16)
     DECODER_RECEPTIVE_FRAMES = 16
 
-    def infer_chunked(self, x, x_lengths, chunk_frames=1024, noise_scale=1, eps=None, halo_frames=None):
+    def infer_chunked(self, x, x_lengths, chunk_frames=1024, noise_scale=1, eps=None, halo_frames=None, *, decoder_precision="fp32"):
         """Long-form inference by time tiling: the mel is cut into chunks of `chunk_frames`, each is
         run with `halo_frames` of real context on both sides, and only the interior samples are kept.  With a halo
         of at least RECEPTIVE_FRAMES every output sample sees exactly the inputs it sees in one-shot `infer`, so the
         result equals it up to fp32 summation order (the library picks tile shapes / K splits from the batch and
         length, e.g. the K-split WN kernel for short chunks, so the two are not guaranteed bit-identical: the test
         bounds the difference at 1e-5 absolute), while the activation workspace stays bounded by the chunk size.
-        Returns the waveform [B, 1, T*hop] only."""
+        Returns the waveform [B, 1, T*hop] only.  ``decoder_precision`` is passed on to every ``infer``."""
+        _decoder_precision(decoder_precision)
         x = N.f32(x)
         B, _, T = x.shape
         halo = self.RECEPTIVE_FRAMES if halo_frames is None else int(halo_frames)
@@ -395,15 +428,15 @@ class SynthesizerTrn(_HipModule):
             e = min(T, s + chunk_frames)
             a, b = max(0, s - halo), min(T, e + halo)
             o = self.infer(x[:, :, a:b].contiguous(), torch.clamp(ln - a, min=0, max=b - a), noise_scale=noise_scale,
-                           eps=eps[:, :, a:b].contiguous())[0]
+                           eps=eps[:, :, a:b].contiguous(), decoder_precision=decoder_precision)[0]
             out[:, :, s * hop:e * hop] = o[:, :, (s - a) * hop:(e - a) * hop]
         return out
 
-    def stream(self, noise_scale=1, halo_frames=None):
+    def stream(self, noise_scale=1, halo_frames=None, *, decoder_precision="fp32"):
         """Incremental long-form inference: ``s = net.stream(noise_scale=.667)``, then ``wave = s.push(mel_chunk)``
         as mel frames arrive and ``wave = s.flush()`` at the end; the concatenated pieces equal one ``infer`` over the whole
         utterance (to fp32 summation order, as ``infer_chunked``).  See :class:`InferStream`."""
-        return InferStream(self, noise_scale=noise_scale, halo_frames=halo_frames)
+        return InferStream(self, noise_scale=noise_scale, halo_frames=halo_frames, decoder_precision=decoder_precision)
 
     def voice_conversion(self, y, y_lengths, sid_src, sid_tgt, eps=None):
         """reference models.py:341-349.  The reference never creates ``emb_g`` (models.py:305-314), so as there this
@@ -429,7 +462,9 @@ class InferStream:
     empty waveform while the look-ahead fills; ``flush`` emits what is left (the true end is zero-padded by the convolutions
     exactly as in a one-shot call).  Every utterance of the batch advances in lock step (all frames of a chunk are valid)."""
 
-    def __init__(self, net, noise_scale=1, halo_frames=None):
+    def __init__(self, net, noise_scale=1, halo_frames=None, *, decoder_precision="fp32"):
+        _decoder_precision(decoder_precision)
+        self.decoder_precision = decoder_precision
         self.net = net
         self.noise_scale = noise_scale
         self.halo = int(net.RECEPTIVE_FRAMES if halo_frames is None else halo_frames)
@@ -447,7 +482,8 @@ class InferStream:
         hop = self.net.dec.hop
         B, _, W = self.mel.shape
         ln = torch.full((B,), W, dtype=torch.int64, device=self.mel.device)
-        o = self.net.infer(self.mel, ln, noise_scale=self.noise_scale, eps=self.eps)[0]
+        kw = {} if self.decoder_precision == "fp32" else {"decoder_precision": self.decoder_precision}   # (the default: the plain call)
+        o = self.net.infer(self.mel, ln, noise_scale=self.noise_scale, eps=self.eps, **kw)[0]
         out = o[:, :, (self.emitted - self.start) * hop:(upto - self.start) * hop].clone()
         self.emitted = upto
         keep_from = max(self.start, self.emitted - self.halo)          # drop what can no longer influence future samples
