@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the SMART-Vocoder inference path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 16] [--frames 512] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 16] [--frames 512] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +10,13 @@ iitp_base, batch 16 x 512 frames per GPU, 22.05 kHz), inputs resident in HBM.  M
 (whole job).  Weak scaling: every rank runs its own 16x512 shard; rank 0 owns the job's batch
 (scattered over RCCL before the timed region) and receives all waveforms (gather inside the timed region).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line; the roofline block it carries is
+priced from the library's counters of the timed region.  --full adds, after the timed region, everything that takes runs of
+its own: at N=1 the dominant kernel's per-launch time, the live HBM-traffic and MFMA-count passes (rocprofv3 --pmc child
+runs), the other single-GPU configurations, the CPU baseline and the whole-batch parity check against the CPU oracle (exit 4
+when it fails); at N>1 the separately timed input scatter and parallel.infer_sharded.  --no-cpu-baseline, --no-pmc and
+--no-other-configs drop single parts of --full.
 
 --dump-outputs DIR: after the timed steps rank 0 writes what the last timed step returned as DIR/<name>.npy (float32):
 at N=1 every output of `infer` (o, x_mask, z, z_p, m_p, logs_p), at N>1 the gathered waveform o.  Inputs and weights are
@@ -185,7 +192,9 @@ def other_configs(net, dev):
 def live_hbm_traffic(B, T, timeout_s=150):
     """Three child runs of this script under `rocprofv3 --pmc` on the DEFAULT launch plan (read-request counters, write-request
     counters, SQ_INSTS_VALU_MFMA_MOPS_F32: separate passes, no tracing beside them), 2 steps each; returns (HBM bytes of the
-    GEMM-family kernels per step, description, fp32 MFMA operations per step as the hardware counted them, in units of 512 FLOP)."""
+    GEMM-family kernels per step, description, fp32 MFMA operations per step as the hardware counted them, in units of 512 FLOP).
+    The children run with --full minus its other legs: the last two steps of their traces, which are counted, are then the
+    dominant-kernel probe's two direct-launch calls."""
     import shutil, subprocess, tempfile
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import pmc_traffic
@@ -201,7 +210,7 @@ def live_hbm_traffic(B, T, timeout_s=150):
         for tag, counters in (("rd", pmc_traffic.READ_COUNTERS), ("wr", pmc_traffic.WRITE_COUNTERS), ("mfma", ["SQ_INSTS_VALU_MFMA_MOPS_F32"])):
             d = os.path.join(base, tag)
             cmd = [prof, "--pmc", *counters, "-d", d, "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__),
-                   "--steps", "2", "--warmup", "1", "--batch", str(B), "--frames", str(T), "--no-cpu-baseline", "--no-pmc", "--no-other-configs"]
+                   "--steps", "2", "--warmup", "1", "--batch", str(B), "--frames", str(T), "--full", "--no-cpu-baseline", "--no-pmc", "--no-other-configs"]
             r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=timeout_s)
             if r.returncode != 0:
                 raise RuntimeError(f"rocprofv3 pass {tag} exit {r.returncode}: {r.stdout[-200:].decode(errors='replace')}")
@@ -251,9 +260,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=16, help="utterances per GPU")
     ap.add_argument("--frames", type=int, default=512, help="mel frames per utterance")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the live HBM-traffic passes (rocprofv3 --pmc child runs of this script)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the C1 / C3 / C5 timings after the timed region")
+    ap.add_argument("--full", action="store_true", help="after the timed region also run every measurement and check beyond the headline "
+                                                          "(dominant kernel, PMC passes, other configs, CPU baseline + parity; N>1: scatter, infer_sharded)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity check against the oracle")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the live HBM-traffic passes (rocprofv3 --pmc child runs of this script)")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the C1 / C3 / C5 timings after the timed region")
     ap.add_argument("--allow-no-collective", action="store_true", help="N>1: do not fail when neither gather nor all_gather works")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float32, <= 64 MB in all)")
     args = ap.parse_args()
@@ -292,7 +303,7 @@ def main():
             cdev = torch.device("cpu")
 
     B, T = args.batch, args.frames
-    sd_np = cases.full_model_weights(skip_enc_q=True)
+    sd_np = cases.full_model_weights(skip_enc_q=True, file_cache=False)
     net = models.SynthesizerTrn(513, 32, n_speakers=109, **cases.IITP_MODEL)
     net.load_state_dict({k: torch.from_numpy(v) for k, v in sd_np.items()}, strict=False)
     net = net.to(dev).eval()
@@ -412,7 +423,7 @@ def main():
     last.clear()
     stats = _native.stats_get()
     scatter_ms = None
-    if use_dist and scatter_ok:
+    if use_dist and scatter_ok and args.full:
         # the other collective of the data path, timed on its own (setup in the weak-scaling protocol, so not inside `value`):
         # rank 0's job batch -> one 16 x T shard per rank, K times, barrier + synchronize on both sides, max over ranks
         full = None
@@ -442,38 +453,39 @@ def main():
         dist.all_gather(allr, mine)
         per_rank = {"step_wall_ms": [float(t[0]) for t in allr], "infer_ms": [float(t[1]) for t in allr], "gather_ms": [float(t[2]) for t in allr],
                     "step_gpu_ms": [float(t[3]) for t in allr]}
-        # The public entry point itself: parallel.infer_sharded (ONE scatter of (lengths | mel | eps) from rank 0 + infer + ONE gather per call,
-        # shapes passed by the caller so that nothing is broadcast or read back), K calls between the same barriers.  A second figure:
-        # `value` stays the weak-scaling step above (inputs resident on every rank), this one moves the job's inputs from rank 0 every call.
-        full = None
-        if rank == 0:
-            full = [torch.from_numpy(sw.synthetic_mel(1001, Bj, T)).to(dev), torch.full((Bj,), T, dtype=torch.int64, device=dev),
-                    torch.from_numpy(sw.synthetic_eps(1001, Bj, T)).to(dev)]
-        sh_out = None
-        if rank == 0:
-            sh_out = torch.empty((Bj, 1, T * net.dec.hop), dtype=torch.float32, device=dev if cdev.type != "cpu" else torch.device("cpu"))
-        try:
-            with torch.no_grad():
-                def sharded_call():
-                    return parallel.infer_sharded(net, full[0] if full else None, full[1] if full else None, full[2] if full else None,
-                                                  noise_scale=0.667, src=0, shape=(Bj, T), out=sh_out)
-                for _ in range(max(1, min(2, args.warmup))):
-                    o_sh = sharded_call()
-                torch.cuda.synchronize(); dist.barrier(); torch.cuda.synchronize()
-                ts = time.perf_counter()
-                for _ in range(args.steps):
-                    o_sh = sharded_call()
-                torch.cuda.synchronize(); dist.barrier(); torch.cuda.synchronize()
-            tsh = torch.tensor([time.perf_counter() - ts], dtype=torch.float64, device=cdev)
-            dist.all_reduce(tsh, op=dist.ReduceOp.MAX)
-            sharded = {"ms_per_call": float(tsh.item()) / args.steps * 1e3, "calls": args.steps,
-                       "samples_per_s": Bj * T * net.dec.hop * args.steps / float(tsh.item()),
-                       "what": "parallel.infer_sharded(shape=(B, T), out=...): scatter of the job's inputs from rank 0 + infer + gather per call, max over ranks"}
+        if args.full:
+            # The public entry point itself: parallel.infer_sharded (ONE scatter of (lengths | mel | eps) from rank 0 + infer + ONE gather per call,
+            # shapes passed by the caller so that nothing is broadcast or read back), K calls between the same barriers.  A second figure:
+            # `value` stays the weak-scaling step above (inputs resident on every rank), this one moves the job's inputs from rank 0 every call.
+            full = None
             if rank == 0:
-                sharded["equals_timed_step_output"] = bool(torch.equal(o_sh.to(out.device), out))
-        except Exception as e:   # noqa: BLE001
-            sharded = {"error": f"{type(e).__name__}: {e}"[:300]}
-        del full
+                full = [torch.from_numpy(sw.synthetic_mel(1001, Bj, T)).to(dev), torch.full((Bj,), T, dtype=torch.int64, device=dev),
+                        torch.from_numpy(sw.synthetic_eps(1001, Bj, T)).to(dev)]
+            sh_out = None
+            if rank == 0:
+                sh_out = torch.empty((Bj, 1, T * net.dec.hop), dtype=torch.float32, device=dev if cdev.type != "cpu" else torch.device("cpu"))
+            try:
+                with torch.no_grad():
+                    def sharded_call():
+                        return parallel.infer_sharded(net, full[0] if full else None, full[1] if full else None, full[2] if full else None,
+                                                      noise_scale=0.667, src=0, shape=(Bj, T), out=sh_out)
+                    for _ in range(max(1, min(2, args.warmup))):
+                        o_sh = sharded_call()
+                    torch.cuda.synchronize(); dist.barrier(); torch.cuda.synchronize()
+                    ts = time.perf_counter()
+                    for _ in range(args.steps):
+                        o_sh = sharded_call()
+                    torch.cuda.synchronize(); dist.barrier(); torch.cuda.synchronize()
+                tsh = torch.tensor([time.perf_counter() - ts], dtype=torch.float64, device=cdev)
+                dist.all_reduce(tsh, op=dist.ReduceOp.MAX)
+                sharded = {"ms_per_call": float(tsh.item()) / args.steps * 1e3, "calls": args.steps,
+                           "samples_per_s": Bj * T * net.dec.hop * args.steps / float(tsh.item()),
+                           "what": "parallel.infer_sharded(shape=(B, T), out=...): scatter of the job's inputs from rank 0 + infer + gather per call, max over ranks"}
+                if rank == 0:
+                    sharded["equals_timed_step_output"] = bool(torch.equal(o_sh.to(out.device), out))
+            except Exception as e:   # noqa: BLE001
+                sharded = {"error": f"{type(e).__name__}: {e}"[:300]}
+            del full
 
     if rank == 0:
         samples_per_step = Bj * T * net.dec.hop
@@ -484,7 +496,7 @@ def main():
         # with HIP events on the launch stream (includes the few % spent in the small non-GEMM kernels).
         conv_tflops = stats["conv_flops"] / (gpu_ms * 1e-3) / 1e12
         exec_tflops = stats["executed_flops"] / (gpu_ms * 1e-3) / 1e12
-        dom, _ = dominant_kernel_probe(net, mel, ln, eps) if (B == 16 and T == 512) else (None, None)
+        dom, _ = dominant_kernel_probe(net, mel, ln, eps) if (args.full and B == 16 and T == 512) else (None, None)
         res = {
             "metric": "audio samples/sec (22.05 kHz), iitp_base batch 16 per GPU",
             "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -552,18 +564,18 @@ def main():
                 "achieved_direct_form": dom["tflops"], "frac_direct_form": dom["tflops"] / FP32_MFMA_PEAK_TFLOPS,
                 "executed_mfma_flop_fraction": executed,
                 "measured": "hipEventRecord around every launch on the launch stream (library event profiler), after the timed region"}
-        # HBM traffic of the same workload from PMC counters.  They cannot be read from inside this process: at N=1 two child runs
+        # HBM traffic of the same workload from PMC counters (--full).  They cannot be read from inside this process: at N=1 two child runs
         # of this script (2 steps, no CPU leg) are made under `rocprofv3 --pmc`, read- and write-request counters in separate
         # passes as MI355X_MICROARCH.md prescribes, and summed per step by tools/pmc_traffic.py.  If the profiler is missing, fails
         # or times out, the figure is taken from this round's committed passes instead and labelled OFFLINE.
         step_bytes, tsrc, mfma_insts = None, None, None
         under_profiler = any(k.startswith(("ROCPROF", "ROCP_TOOL")) for k in os.environ)      # never nest profilers
-        if world == 1 and not args.no_pmc and not under_profiler and B == 16 and T == 512:
+        if args.full and world == 1 and not args.no_pmc and not under_profiler and B == 16 and T == 512:
             try:
                 step_bytes, tsrc, mfma_insts = live_hbm_traffic(B, T)
             except Exception as e:   # noqa: BLE001
                 res["roofline"]["traffic_live_error"] = f"{type(e).__name__}: {e}"[:300]
-        if step_bytes is None:
+        if args.full and step_bytes is None:
             import glob
             tfiles = sorted(glob.glob(os.path.join(ROOT, "profiles", f"{ROUND_TAG}*_pmc_hbm_traffic.json")))
             if tfiles and B == 16 and T == 512:
@@ -584,13 +596,13 @@ def main():
             res["roofline"]["traffic_unit"] = "HBM bytes per GEMM-family launch (mean over gemm_launches_per_step)"
             res["roofline"]["traffic_bytes_per_step"] = step_bytes
             res["roofline"]["traffic_source"] = tsrc
-        if world == 1 and B == 16 and T == 512 and not args.no_other_configs and not under_profiler:
+        if args.full and world == 1 and B == 16 and T == 512 and not args.no_other_configs and not under_profiler:
             try:
                 res["other_configs"] = other_configs(net, dev)
             except Exception as e:   # noqa: BLE001
                 res["other_configs"] = {"error": f"{type(e).__name__}: {e}"[:300]}
         fail = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             keep = {}
             res["cpu_baseline"] = cpu_baseline(sd_np, 1001, keep)
             if B == 16 and T == 512 and "c2" in keep:

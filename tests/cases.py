@@ -324,13 +324,18 @@ def full_model_shapes():
 _FULL_SD = {}
 
 
-def full_model_weights(seed=WEIGHT_SEED, skip_enc_q=True):
-    """Synthetic iitp_base weights as {name: float32 ndarray}; enc_q (unused by infer) skipped by default."""
+def full_model_weights(seed=WEIGHT_SEED, skip_enc_q=True, file_cache=True):
+    """Synthetic iitp_base weights as {name: float32 ndarray}; enc_q (unused by infer) skipped by default.  file_cache=False
+    generates them in this process and neither reads nor writes the shared file below (bench.py: a run reads nothing an
+    earlier run wrote); the values are the same either way."""
     key = (seed, skip_enc_q)
     if key not in _FULL_SD:
         shapes = full_model_shapes()
         if skip_enc_q:
             shapes = {k: v for k, v in shapes.items() if not k.startswith("enc_q.")}
+        if not file_cache:
+            _FULL_SD[key] = sw.fill_state_dict(shapes, seed=seed)
+            return _FULL_SD[key]
         # The variant suite starts ~25 processes that all need these 142 MB: generated once per box, then read back from /tmp
         # (file name = digest of the generator's source, the seed and the shape list, so a change of any of them regenerates)
         import hashlib, tempfile

@@ -1,6 +1,6 @@
 """bench.py --dump-outputs without a GPU: the writer keeps whole arrays under its 64 MB cap, and above it a seeded sample that is
-the same in every run; bench.py refuses a step count that would time nothing.  (The GPU run of the option itself:
-tests/test_parallel_gpu.py::test_bench_single_gpu_line_schema.)"""
+the same in every run; bench.py refuses a step count that would time nothing.  (The GPU runs of the option itself:
+tests/test_parallel_gpu.py::test_bench_plain_line and ::test_bench_single_gpu_line_schema.)"""
 import os
 import subprocess
 import sys
@@ -46,3 +46,18 @@ def test_steps_must_time_at_least_one_step():
     r = subprocess.run([sys.executable, os.path.join(cases.ROOT, "bench.py"), "--steps", "0"], stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode == 2 and "--steps" in r.stderr, r.stderr[-2000:]
+
+
+def test_bench_weights_are_generated_in_process(tmp_path, monkeypatch):
+    """bench.py takes its weights from cases.full_model_weights(file_cache=False): generated in the run's own process, with no file
+    read or written, and equal to what the file-cached path hands the tests."""
+    import tempfile
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path))
+    monkeypatch.setattr(cases, "_FULL_SD", {})
+    fresh = cases.full_model_weights(skip_enc_q=True, file_cache=False)
+    assert os.listdir(tmp_path) == []
+    cases.full_model_weights(skip_enc_q=True)                       # generates and writes the file ...
+    monkeypatch.setattr(cases, "_FULL_SD", {})
+    cached = cases.full_model_weights(skip_enc_q=True)              # ... which this call reads back
+    assert len(os.listdir(tmp_path)) == 1
+    assert list(fresh) == list(cached) and all(fresh[k].dtype == np.float32 and np.array_equal(fresh[k], cached[k]) for k in fresh)

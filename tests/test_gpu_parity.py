@@ -812,7 +812,7 @@ def test_full_size_properties(M, net):
 def test_c2_full_size_vs_oracle(M, net):
     """BASELINE.json configs[1] - the bench workload itself, 16 x 512 frames, seed 1001 (exactly bench.py's tensors) - run as ONE batch on the GPU and
     compared with the CPU oracle on four of its utterances (0, 5, 10, 15; the oracle treats utterances independently, and it needs 10-40 s for all
-    sixteen - `bench.py` does that whole-batch comparison on every bench run, and `test_full_size_vs_reference_fixture[c2_16x512]` covers every sample
+    sixteen - `bench.py --full` does that whole-batch comparison on every run, and `test_full_size_vs_reference_fixture[c2_16x512]` covers every sample
     of the batch against numbers the reference itself produced): waveform RMS <= 1e-3 (north_star) and relative RMS <= 1e-4, latents to the
     per-module tolerance."""
     Bn, Tn = 16, 512

@@ -97,12 +97,12 @@ def test_infer_sharded_equals_single_process_on_one_gpu():
 
 
 def test_bench_two_ranks_gloo_one_gpu(tmp_path):
-    """bench.py --gpus 2 under torch.distributed.run with both ranks on device 0 (BENCH_BACKEND=gloo): the scatter, the
+    """bench.py --gpus 2 --full under torch.distributed.run with both ranks on device 0 (BENCH_BACKEND=gloo): the scatter, the
     per-rank infer and the gather inside the timed region all execute; the JSON line must report collective == gather."""
     env = dict(os.environ, BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(cases.ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "4", "--frames", "128"]
+           "--batch", "4", "--frames", "128", "--full"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -118,12 +118,12 @@ def test_bench_two_ranks_gloo_one_gpu(tmp_path):
 
 
 def test_bench_two_ranks_one_gpu_full_size_bits():
-    """bench.py --gpus 2 with both ranks on ONE device at the headline shape (16 x 512 per rank): the persistent WN stack launches (csrc/wn_stack.hip)
+    """bench.py --gpus 2 --full with both ranks on ONE device at the headline shape (16 x 512 per rank): the persistent WN stack launches (csrc/wn_stack.hip)
     of the two processes then compete for the CUs, and their workgroups wait for neighbours that are not resident yet.  `parallel.infer_sharded` must
     still return the timed step's bits (round 5: with halo slots reused by layer parity it did not)."""
     env = dict(os.environ, BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(cases.ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2"]
+           "--master-port", str(_free_port()), os.path.join(cases.ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--full"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -181,12 +181,12 @@ def test_two_processes_one_gpu_alternating_inputs():
 
 
 def test_bench_single_gpu_line_schema(tmp_path):
-    """bench.py at N=1 on the timed configuration (16 x 512, 2 steps, no CPU leg): ONE JSON line with the contract's keys, the
+    """bench.py --full at N=1 on the timed configuration (16 x 512, 2 steps, no CPU leg): ONE JSON line with the contract's keys, the
     roofline block (`frac` = executed multiply-adds over the peak, bounded by 1; `frac_direct_form`, which the Winograd kernels may
     push above 1), the library's launch statistics, the HBM traffic of the step and the hardware's MFMA count of the default plan
     (live PMC passes; the count must agree with the library's bookkeeping to 1.5 %), and the C1 / C3 / C5 timings.  --dump-outputs
     writes every output of the last timed step's `infer`, whole, as float32."""
-    cmd = [sys.executable, os.path.join(cases.ROOT, "bench.py"), "--steps", "2", "--warmup", "2", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(cases.ROOT, "bench.py"), "--steps", "2", "--warmup", "2", "--full", "--no-cpu-baseline",
            "--dump-outputs", str(tmp_path / "dump")]
     r = subprocess.run(cmd, env=dict(os.environ), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -213,13 +213,42 @@ def test_bench_single_gpu_line_schema(tmp_path):
     # HBM traffic: live rocprofv3 --pmc child runs (or, should the profiler fail on the box, this round's committed passes)
     assert rf["traffic"] is not None and rf["traffic_source"].startswith(("LIVE", "OFFLINE")), rf
     assert 2e10 < rf["traffic_bytes_per_step"] < 8e10, rf["traffic_bytes_per_step"]
+    _check_headline_dump(j, tmp_path / "dump")
+
+
+def _check_headline_dump(j, d):
+    """--dump-outputs at 16 x 512, N=1: every output of the last timed step's `infer`, whole, as float32, 64 MB at most."""
     dump = j["dump_outputs"]["arrays"]
     shapes = {"o": (16, 1, 512 * 256), "x_mask": (16, 1, 512), "z": (16, 192, 512), "z_p": (16, 192, 512), "m_p": (16, 192, 512), "logs_p": (16, 192, 512)}
-    assert sorted(os.listdir(tmp_path / "dump")) == sorted(f"{n}.npy" for n in shapes) and not any(v["sampled"] for v in dump.values()), dump
+    assert sorted(os.listdir(d)) == sorted(f"{n}.npy" for n in shapes) and not any(v["sampled"] for v in dump.values()), dump
     for n, sh in shapes.items():
-        a = np.load(tmp_path / "dump" / f"{n}.npy")
+        a = np.load(d / f"{n}.npy")
         assert a.dtype == np.float32 and a.shape == sh and np.isfinite(a).all(), n
-    assert sum(os.path.getsize(tmp_path / "dump" / f) for f in os.listdir(tmp_path / "dump")) <= 64e6
+    assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64e6
+
+
+def test_bench_plain_line(tmp_path):
+    """bench.py at N=1 without --full (the run that measures the headline): ONE JSON line with the contract's keys, `value` and
+    `ms_per_step` of the same steps, the roofline figures priced from the library's counters of the timed region, --dump-outputs
+    written whole - and nothing that takes runs of its own: no dominant-kernel probe, PMC passes, other configurations, CPU
+    baseline or parity check."""
+    cmd = [sys.executable, os.path.join(cases.ROOT, "bench.py"), "--steps", "2", "--warmup", "2", "--dump-outputs", str(tmp_path / "dump")]
+    r = subprocess.run(cmd, env=dict(os.environ), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+              "data", "config", "roofline"):
+        assert k in j, k
+    assert j["n_gpus"] == 1 and j["steps"] == 2 and j["warmup"] == 2 and j["dtype"] == "f32" and j["unit"] == "samples/s" and j["higher_is_better"] is True
+    assert j["value"] > 0 and abs(j["value"] * j["ms_per_step"] * 1e-3 / j["config"]["samples_per_step"] - 1.0) < 1e-9
+    rf = j["roofline"]
+    assert 0.0 < rf["frac"] <= 1.0 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-9
+    assert abs(rf["flop_per_step"] - 2568280.0 * j["config"]["samples_per_step"]) / rf["flop_per_step"] < 0.01
+    assert "dominant_kernel" not in rf and rf["traffic"] is None and rf["executed_flops_pmc"] is None, rf
+    assert not any(k in j for k in ("other_configs", "cpu_baseline", "parity")), sorted(j)
+    _check_headline_dump(j, tmp_path / "dump")
 
 
 _RCCL_WORLD1 = r'''
@@ -273,12 +302,12 @@ def test_rccl_world_size_one_on_device(tmp_path):
 
 
 def test_bench_one_rank_rccl():
-    """bench.py launched by torch.distributed.run with ONE rank and BENCH_BACKEND=nccl (BENCH_FORCE_DIST=1): process group, packed
+    """bench.py --full launched by torch.distributed.run with ONE rank and BENCH_BACKEND=nccl (BENCH_FORCE_DIST=1): process group, packed
     scatter and the waveform gather inside the timed region run over RCCL; the line reports collective == gather."""
     env = dict(os.environ, BENCH_BACKEND="nccl", BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(cases.ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--batch", "4", "--frames", "128", "--no-cpu-baseline", "--no-pmc", "--no-other-configs"]
+           "--batch", "4", "--frames", "128", "--full", "--no-cpu-baseline", "--no-pmc", "--no-other-configs"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -335,7 +364,7 @@ print(f"RCCL2 rank{rank} " + json.dumps(res))
 def test_rccl_two_devices(tmp_path):
     """SURVEY 8e on real hardware, the first time two devices are visible: torchrun with one rank PER DEVICE over "nccl" (= RCCL),
     the packed scatter and the in-place gather move bytes between two GPUs, and `infer_sharded(shape=..., bitwise=True)` must return the bits a
-    single process computes for the whole job - at an uneven split and at the headline shape.  Then `bench.py --gpus 2` end to end with
+    single process computes for the whole job - at an uneven split and at the headline shape.  Then `bench.py --gpus 2 --full` end to end with
     collective == "gather".  Every other multi-rank test of this file pins both ranks to cuda:0 or talks over gloo."""
     script = tmp_path / "rccl2.py"
     script.write_text(_RCCL_WORLD2)
@@ -351,7 +380,7 @@ def test_rccl_two_devices(tmp_path):
         res = json.loads(l.split(" ", 2)[2])
         assert res and all(res.values()), l
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(cases.ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2"]
+           "--master-port", str(_free_port()), os.path.join(cases.ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--full"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
