@@ -823,7 +823,9 @@ int launch_conv_wino_group(const PackedWino* const* pws, const ConvArgs* as, int
     int w0 = 0, nw = 0;
     const int full = wino4_tail_plan(as[0].Ncols, dil, wino4_nc(*pws[0]), &w0, &nw);
     bool ok = full > 0;
-    for (int i = 0; i < n; ++i) ok = ok && pws[i]->wraw.p && as[i].Ncols == as[0].Ncols && !(g4.a[i].flags & (F_RES | F_ACC | F_DIV)) && pws[i]->Cin * pws[i]->K * 32 <= 160 * 1024;
+    // the tail launch takes L and the pre-activation slope from member 0 for every member (conv_wino4.hip wino4_launch_tail)
+    for (int i = 0; i < n; ++i) ok = ok && pws[i]->wraw.p && as[i].Ncols == as[0].Ncols && as[i].Lin == as[0].Lin && as[i].pre_slope == as[0].pre_slope &&
+                                  !(g4.a[i].flags & (F_RES | F_ACC | F_DIV)) && pws[i]->Cin * pws[i]->K * 32 <= 160 * 1024;
     if (ok) {
       const long long G = device_cu_count(), bv = variant_batch(B);
       long long per_b = 0, per_b_drop = 0;

@@ -204,6 +204,28 @@ def spline_inputs(case):
     return x, uw, uh, ud
 
 
+# ---------------------------------------------------------------- one MRF stage in isolation
+# tests/test_gpu_mrf_forms.py runs every launch form of the MRF (csrc/engine.hip Generator::run_mrf_grouped) against a float64 oracle;
+# tests/test_mrf_bounds_cpu.py shows on the CPU that these bounds see a reduced-precision operand stream.  Both compare the waveform of
+# a one-upsampler Generator (conv_pre 32 -> 2C, one ConvTranspose1d 2C -> C with stride 2, the three ResBlock1 chains at C, conv_post).
+MRF_REL_RMS = 3.5e-6     # R: rel-RMS of the compared rows against float64, 2x the worst fp32 form measured (C = 256, 1.73e-6)
+MRF_MAX_ERR = 3.5e-5     # A: max|err| <= A * rms(ref), 10x R (worst measured 7.6e-6); per-form figures: tests/test_gpu_mrf_forms.py
+
+
+def mrf_stage_config(C):
+    return dict(initial_channel=32, resblock="1", rks=[3, 7, 11], rds=[[1, 3, 5]] * 3, ur=[2], uic=2 * C, uks=[4], gin=0)
+
+
+def mrf_stage_weights(C, seed=None):
+    """(config, {name: float32 ndarray}) of the one-stage Generator at C; unit gains keep tanh(conv_post) well inside its linear range."""
+    c = mrf_stage_config(C)
+    return c, sw.fill_state_dict(generator_shapes(c), 12000 + C if seed is None else seed, 1.0)
+
+
+def mrf_stage_input(C, B, T, seed=0):
+    return rnd(12100 + C + seed, "x", (B, 32, T), 1.0)
+
+
 # ---------------------------------------------------------------- state-dict shape builders
 # (names and shapes as the reference modules register them; verified against
 #  tests/golden/state_dict_layout.json and by make_golden.py's load_state_dict)
