@@ -884,7 +884,8 @@ int launch_wn_layer_fused(const PackedConv& in_l, const PackedConv& rs_l, int H,
   int prof_idx = -1;
   if (prof_enabled()) {
     char d[160];
-    snprintf(d, sizeof(d), "fusedWN H%-4d k%-2d d%-2d N%-7d B%-3d NA%d%s%s%s", H, in_l.ktaps, in_l.dil, T, B, NA, ksplit ? " ksplit" : "", f25 ? " F(2,5)" : "", last ? " last" : "");
+    snprintf(d, sizeof(d), "fusedWN H%-4d k%-2d d%-2d N%-7d B%-3d NA%d%s%s%s%s", H, in_l.ktaps, in_l.dil, T, B, NA, ksplit ? " ksplit" : "", f25 ? " F(2,5)" : "",
+             last ? " last" : "", gadd ? (gadd_ts ? " gT" : " g1") : "");      // (g1 / gT: conditioned by one frame of g / by T frames)
     prof_idx = prof_begin(st, d, flops);
   }
   if (f25) {

@@ -424,16 +424,18 @@ int launch_wn_small_layer(const PackedConv& in_l, const float* wpf, const float*
   // half of the 1 x 1 six times on 48 of 32 columns, its skip half once
   const double fin = in_l.flops_per_col * (double)B * (double)T, frs = ap ? rs_flops_per_col * (double)B * (double)T : 0.0;
   stats_add_conv(fin + frs, ap ? 2 : 1, 0.6 * fin + (0.5 * 6.0 * 1.5 + 0.5) * frs);
-  int prof_idx = -1;
-  if (prof_enabled()) {
-    char d[160];
-    snprintf(d, sizeof(d), "smallWN H192  k5  d1  N%-7d B%-3d F(2,5)%s", T, B, ap ? " + res_skip" : "");
-    prof_idx = prof_begin(st, d, fin + frs);
-  }
   // two row pairs per workgroup when that makes ONE round of workgroups out of two (43 .. 85 tiles on 256 CUs; bit-identical to one pair each)
   const long long tiles = (long long)variant_batch(B) * ((T + 31) / 32);
   const int ncu = device_cu_count();
-  if (wn_small_two_pairs() && tiles * 6 > ncu && tiles * 3 <= ncu) {
+  const bool pp2 = wn_small_two_pairs() && tiles * 6 > ncu && tiles * 3 <= ncu;
+  int prof_idx = -1;
+  if (prof_enabled()) {   // (pp2: two row pairs per workgroup; g1 / gT: conditioned by one frame of g / by T frames)
+    char d[160];
+    snprintf(d, sizeof(d), "smallWN H192  k5  d1  N%-7d B%-3d F(2,5)%s%s%s", T, B, ap ? " + res_skip" : "", pp2 ? " pp2" : "",
+             gadd ? (gadd_ts ? " gT" : " g1") : "");
+    prof_idx = prof_begin(st, d, fin + frs);
+  }
+  if (pp2) {
     auto kern = wn_small_f25_kernel<2>;
     SVOC_TRY(ensure_max_dyn_lds((const void*)kern));
     hipLaunchKernelGGL(kern, dim3((T + 31) / 32, 3, B), dim3(768), (size_t)WNS_LDS_FLOATS * sizeof(float), st, a);

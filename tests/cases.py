@@ -226,6 +226,13 @@ def mrf_stage_input(C, B, T, seed=0):
     return rnd(12100 + C + seed, "x", (B, 32, T), 1.0)
 
 
+# ---------------------------------------------------------------- WN launch forms
+# tests/test_gpu_wn_forms.py runs every launch form of the WN stack (csrc/engine.hip WNStack::forward) against a float64 oracle;
+# tests/test_wn_bounds_cpu.py shows on the CPU that these bounds admit the F(2,5) in_layer's fp32 error and refuse a 1e-5 gate defect.
+WN_REL_RMS = 2e-6        # R: rel-RMS of the compared rows' valid columns against float64, 2.8x the worst form measured (16-layer stack, 7.1e-7)
+WN_MAX_ERR = 2e-5        # A: max|err| <= A * rms(ref), 10x R (worst measured 4.4e-6); per-form figures: tests/test_gpu_wn_forms.py
+
+
 # ---------------------------------------------------------------- state-dict shape builders
 # (names and shapes as the reference modules register them; verified against
 #  tests/golden/state_dict_layout.json and by make_golden.py's load_state_dict)
