@@ -239,6 +239,45 @@ int svoc_synth_set_decoder_precision(svoc_synth* h, int mode);
 int svoc_synth_plan_stats(svoc_synth* h, int64_t* out5);
 void svoc_synth_destroy(svoc_synth* h);
 
+/* ---- stateful streaming inference: SynthesizerTrn.infer fed chunk by chunk (additions only: svoc_abi_version stays 7) ---------
+ * Replaces nothing in the reference (its only hook for partial decoding is max_len, models.py:338).  The path is cut into stages - mel
+ * encoder (-> z_p), each reverse coupling, conv_pre, each upsampler + MRF, conv_post + tanh - and every stage boundary keeps, in
+ * stream-owned device buffers, only the columns the next stage still needs.  A push runs each stage over its new columns plus that
+ * stage's own halo; the concatenated pieces plus the flush equal one svoc_synth_infer over the whole utterance (lengths = T, max_len
+ * none) to fp32 summation order.
+ *
+ * svoc_stream_geometry: host only (no device, no handle).  Writes up to n ints of {S, lookahead_frames, hop, then per stage s < S:
+ * u_s, rate_s, h_left_s, h_right_s} and returns the number the whole description needs (3 + 4 S), or a negative svoc_status.
+ * Stage s turns input column m into output columns at u_s per input (rate_s: output columns per mel frame), and its output column n
+ * depends on exactly the input columns m with n - h_left_s <= m * u_s <= n + h_right_s (ConvTranspose1d index arithmetic, the
+ * widest ResBlock chain of the configured kind).  lookahead_frames = ceil(sum_s h_right_s / rate_s): after a push, every sample of
+ * the frames up to (frames pushed - lookahead_frames) has been returned.
+ *
+ * A stream belongs to one synth handle and a fixed batch B: every utterance of the batch advances in lock step, all frames valid
+ * (no lengths, no max_len, no conditioning).  It uses the handle's weights and module workspaces, and the handle's decoder precision
+ * (svoc_synth_set_decoder_precision) at the time of each push; svoc_synth_infer calls and other streams of the same handle may be
+ * interleaved with its pushes, one at a time on one hipStream_t (the handle's rule).  Destroy the stream before its synth handle.
+ *
+ * Blocking behaviour: svoc_stream_create allocates every buffer for pushes of up to max_chunk_frames frames (and sizes the handle's
+ * workspaces for its windows) and blocks; push and flush only enqueue - no allocation, no synchronisation - and split a push larger
+ * than max_chunk_frames into pieces on the host.  svoc_stream_samples is host only: the number of samples per utterance the next
+ * push of T frames (flush != 0: the flush, T = 0) writes, a function of the push sizes alone.
+ *
+ * push: mel [B, n_mel, T], eps [B, inter_channels, T] (the N(0,1) draw of svoc_synth_infer; required), contiguous device memory;
+ * writes samples [0, n) of every row of out [B][out_ld] and n to *n_samples; n > out_ld fails with SVOC_ERR_SHAPE before any launch.
+ * flush: runs every stage to the true end (the convolutions' zero padding, as in one call) and leaves the stream empty: the next push
+ * starts a new utterance with zero left context.  stats: columns[s] = input columns stage s has processed so far (windows included),
+ * *state_bytes = the device memory the stream owns (constant); returns S. */
+typedef struct svoc_stream svoc_stream;
+int svoc_stream_geometry(const svoc_synth_config* cfg, int* out, int n);
+int svoc_stream_create(svoc_stream** out, svoc_synth* synth, int B, int max_chunk_frames);
+int svoc_stream_samples(svoc_stream* s, int T, int flush, int64_t* n_samples);
+int svoc_stream_push(svoc_stream* s, void* stream, const float* mel, const float* eps, int T, float noise_scale, float* out,
+                     int64_t out_ld, int64_t* n_samples);
+int svoc_stream_flush(svoc_stream* s, void* stream, float noise_scale, float* out, int64_t out_ld, int64_t* n_samples);
+int svoc_stream_stats(svoc_stream* s, int64_t* columns, int n, int64_t* state_bytes);
+void svoc_stream_destroy(svoc_stream* s);
+
 /* ---- models.PosteriorEncoder (models.py:83-112): not on the infer path; enc_q of training / voice conversion ---- */
 typedef struct svoc_posterior svoc_posterior;
 /* tensors: pre.{weight,bias}, enc.<WN tensors>, proj.{weight,bias} */

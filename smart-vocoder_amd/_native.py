@@ -86,6 +86,13 @@ SIGNATURES = {
     "svoc_synth_plan_stats": (_I, [_P, C.POINTER(_L)]),
     "svoc_synth_destroy": (None, [_P]),
     "svoc_synth_set_decoder_precision": (_I, [_P, _I]),
+    "svoc_stream_geometry": (_I, [C.POINTER(svoc_synth_config), C.POINTER(C.c_int), _I]),
+    "svoc_stream_create": (_I, [C.POINTER(_P), _P, _I, _I]),
+    "svoc_stream_samples": (_I, [_P, _I, _I, C.POINTER(_L)]),
+    "svoc_stream_push": (_I, [_P, _P, _P, _P, _I, _F, _P, _L, C.POINTER(_L)]),
+    "svoc_stream_flush": (_I, [_P, _P, _F, _P, _L, C.POINTER(_L)]),
+    "svoc_stream_stats": (_I, [_P, C.POINTER(_L), _I, C.POINTER(_L)]),
+    "svoc_stream_destroy": (None, [_P]),
     "svoc_posterior_create": (_I, [C.POINTER(_P), _I, _I, _I, _I, _I, _I, _I, *_TAB, C.c_char_p]),
     "svoc_posterior_forward": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I]),
     "svoc_posterior_destroy": (None, [_P]),

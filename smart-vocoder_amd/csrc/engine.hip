@@ -807,6 +807,84 @@ struct Generator {
 
   int reserve(int B, int T) { return ws.ensure(workspace_bytes(B, T)); }
 
+  // conv_pre (+ cond(g), gbias: its [B][ch] result or null) (models.py:142-144): x [B][initial_channel][x_ld] -> y [B][ch][y_ld]
+  int run_pre(hipStream_t st, const float* x, long long x_bs, int x_ld, const float* in_mask, long long in_mask_bs, const float* gbias,
+              float* y, long long y_bs, int y_ld, int B, int T) {
+    const int ch = cfg.upsample_initial_channel;
+    ConvArgs a = mk_args();
+    set_in(a, x, x_bs, x_ld, T);
+    a.in_mask = in_mask; a.in_mask_bs = in_mask_bs;
+    a.Ncols = T;
+    set_out(a.out[0], y, y_bs, y_ld, ch);
+    if (gbias) { a.gadd = gbias; a.gadd_bs = ch; a.gadd_ld = 1; a.gadd_ts = 0; }
+    // k = 7, 192 -> 512 channels: the F(4,4) kernel issues half the direct form's MFMAs (114 -> ~55 us at 16 x 512); from half a tile per CU on
+    int done = 1;
+    if (conv_pre_w && !in_mask && !gbias) {
+      done = launch_conv_wino(*conv_pre_w, a, B, 1, st, mrf_min_tiles());
+      if (done < 0) return done;
+    }
+    if (done == 1) SVOC_TRY(launch_conv(conv_pre, a, B, st));
+    return SVOC_OK;
+  }
+
+  // Upsampler i + its MRF (models.py:145-155): R [B][ch_i][R_ld] (L columns) -> XS [B][ch_i / 2][stage_ld(L * u_i)].  X: the upsampler's
+  // output; A1 / B1: the ResBlock scratch of the single-chain plan (forward() hands it R as B1); bufs: the workspace's buffers (chain
+  // scratch of the multi-stream plan).  Shared by forward() and the stateful stream (stream.hip), which runs it over a window.
+  int run_stage(hipStream_t st, int i, const float* R, long long R_bs, int R_ld, float* X, float* XS, float* A1, float* B1,
+                const std::vector<float*>& bufs, int B, int L) {
+    int ch = cfg.upsample_initial_channel;
+    for (int q = 0; q < i; ++q) ch /= 2;
+    const int u = cfg.upsample_rates[i];
+    const int Lo = L * u, ldo = stage_ld(Lo), cho = ch / 2;
+    int ups_done = 1;
+    if (ups_w[i]) {   // lrelu(0.1) -> ConvTranspose1d, Winograd F(4,2) over the polyphase filters (models.py:147-148)
+      ups_done = launch_convt_wino(*ups_w[i], R, R_bs, R_ld, 0.1f, X, (long long)cho * ldo, ldo, B, L, st);
+      if (ups_done < 0) return ups_done;
+    }
+    if (ups_done == 1) {   // ... as the direct polyphase GEMM
+      ConvArgs a = mk_args();
+      set_in(a, R, R_bs, R_ld, L);
+      a.pre_slope = 0.1f;
+      a.mode = EPI_UPS;
+      a.Lout = Lo;
+      a.Ncols = (Lo - 1 + ups[i]->ups_pad) / u + 1;
+      set_out(a.out[0], X, (long long)cho * ldo, ldo, cho * u);
+      SVOC_TRY(launch_conv(*ups[i], a, B, st));
+    }
+    const long long bs = (long long)cho * ldo;
+    // Short inputs: when the three chains' convolutions are too small for the grouped Winograd launches (fewer than half a
+    // workgroup per CU in total: mrf_min_tiles()) they would run one by one as K-split launches; the chains are independent until the
+    // final accumulate, so they go to the three chain streams instead and their latencies overlap.
+    bool small_stage = false;
+    {
+      static const bool on = !(getenv("SVOC_MRF_SMALL") && atoi(getenv("SVOC_MRF_SMALL")) == 0);
+      const int mtl = cho / 32, wm = (mtl >= 4 && mtl % 4 == 0) ? 4 : 2;
+      long long tiles = (long long)cfg.n_kernels * variant_batch(B) * ((Lo + (wm == 4 ? 63 : 127)) / (wm == 4 ? 64 : 128)) * ((mtl + wm - 1) / wm);
+      if (mtl == 1) tiles = (long long)cfg.n_kernels * variant_batch(B) * ((Lo + 511) / 512);    // F(4,3), one row tile: 512 outputs per workgroup tile
+      small_stage = on && (tiles < mrf_min_tiles() || (mtl == 1 && (Lo & 3)));
+    }
+    // fp16 mode: the chains always run on the stream plan below, one conv_f16.hip launch per convolution
+    if (use_streams && !small_stage && precision == SVOC_PREC_F32 && mrf_grouped(i, cho)) {
+      // MRF with the chains' step-i convolutions grouped into single launches (conv_group_kernel)
+      return run_mrf_grouped(st, i, X, XS, bufs, bs, ldo, cho, B, Lo);
+    }
+    if (use_streams) SVOC_HIP(hipEventRecord(ev_fork, st));
+    for (int j = 0; j < cfg.n_kernels; ++j) {   // MRF: xs = sum_j ResBlock_j(x); x = xs / n (models.py:149-155)
+      ResSink sink{XS, bs, ldo, 0u, 1.0f};
+      if (j > 0) sink.flags |= F_ACC;
+      if (j == cfg.n_kernels - 1) { sink.flags |= F_DIV; sink.div = (float)cfg.n_kernels; }
+      if (use_streams) {
+        SVOC_HIP(hipStreamWaitEvent(chain_st[j], ev_fork, 0));
+        SVOC_TRY(rbs[i * cfg.n_kernels + j]->run(chain_st[j], X, bs, ldo, nullptr, 0, bufs[3 + 2 * j], bufs[4 + 2 * j], bs, ldo, sink, B, Lo,
+                                                 j > 0 ? chain_done[j - 1] : nullptr, chain_done[j]));
+      } else {
+        SVOC_TRY(rbs[i * cfg.n_kernels + j]->run(st, X, bs, ldo, nullptr, 0, A1, B1, bs, ldo, sink, B, Lo));
+      }
+    }
+    if (use_streams) SVOC_HIP(hipStreamWaitEvent(st, chain_done[cfg.n_kernels - 1], 0));
+    return SVOC_OK;
+  }
+
   int forward(hipStream_t st, const float* x, int x_ld, long long x_bs, const float* in_mask, long long in_mask_bs,
               const float* g, float* out, int B, int T) {
     const size_t sf = stage_floats(T);
@@ -829,78 +907,16 @@ struct Generator {
       set_out(a.out[0], gbias, ch, 1, ch);
       SVOC_TRY(launch_conv(*cond, a, B, st));
     }
-    {   // conv_pre (+ cond(g)) (models.py:142-144)
-      ConvArgs a = mk_args();
-      set_in(a, x, x_bs, x_ld, T);
-      a.in_mask = in_mask; a.in_mask_bs = in_mask_bs;
-      a.Ncols = T;
-      set_out(a.out[0], bufs[r], (long long)ch * ld, ld, ch);
-      if (g) { a.gadd = gbias; a.gadd_bs = ch; a.gadd_ld = 1; a.gadd_ts = 0; }
-      // k = 7, 192 -> 512 channels: the F(4,4) kernel issues half the direct form's MFMAs (114 -> ~55 us at 16 x 512); from half a tile per CU on
-      int done = 1;
-      if (conv_pre_w && !in_mask && !g) {
-        done = launch_conv_wino(*conv_pre_w, a, B, 1, st, mrf_min_tiles());
-        if (done < 0) return done;
-      }
-      if (done == 1) SVOC_TRY(launch_conv(conv_pre, a, B, st));
-    }
+    SVOC_TRY(run_pre(st, x, x_bs, x_ld, in_mask, in_mask_bs, g ? gbias : nullptr, bufs[r], (long long)ch * ld, ld, B, T));   // conv_pre (+ cond(g)) (models.py:142-144)
     for (int i = 0; i < cfg.n_upsamples; ++i) {
       const int u = cfg.upsample_rates[i];
       float *R, *X, *XS;
       if (use_streams) { R = bufs[r]; XS = bufs[r ^ 1]; X = bufs[2]; }
       else { R = bufs[r]; X = bufs[(r + 1) & 3]; XS = bufs[(r + 2) & 3]; }
-      const int Lo = L * u, ldo = stage_ld(Lo), cho = ch / 2;
-      int ups_done = 1;
-      if (ups_w[i]) {   // lrelu(0.1) -> ConvTranspose1d, Winograd F(4,2) over the polyphase filters (models.py:147-148)
-        ups_done = launch_convt_wino(*ups_w[i], R, (long long)ch * ld, ld, 0.1f, X, (long long)cho * ldo, ldo, B, L, st);
-        if (ups_done < 0) return ups_done;
-      }
-      if (ups_done == 1) {   // ... as the direct polyphase GEMM
-        ConvArgs a = mk_args();
-        set_in(a, R, (long long)ch * ld, ld, L);
-        a.pre_slope = 0.1f;
-        a.mode = EPI_UPS;
-        a.Lout = Lo;
-        a.Ncols = (Lo - 1 + ups[i]->ups_pad) / u + 1;
-        set_out(a.out[0], X, (long long)cho * ldo, ldo, cho * u);
-        SVOC_TRY(launch_conv(*ups[i], a, B, st));
-      }
-      const long long bs = (long long)cho * ldo;
-      // Short inputs: when the three chains' convolutions are too small for the grouped Winograd launches (fewer than half a
-      // workgroup per CU in total: mrf_min_tiles()) they would run one by one as K-split launches; the chains are independent until the
-      // final accumulate, so they go to the three chain streams instead and their latencies overlap.
-      bool small_stage = false;
-      {
-        static const bool on = !(getenv("SVOC_MRF_SMALL") && atoi(getenv("SVOC_MRF_SMALL")) == 0);
-        const int mtl = cho / 32, wm = (mtl >= 4 && mtl % 4 == 0) ? 4 : 2;
-        long long tiles = (long long)cfg.n_kernels * variant_batch(B) * ((Lo + (wm == 4 ? 63 : 127)) / (wm == 4 ? 64 : 128)) * ((mtl + wm - 1) / wm);
-        if (mtl == 1) tiles = (long long)cfg.n_kernels * variant_batch(B) * ((Lo + 511) / 512);    // F(4,3), one row tile: 512 outputs per workgroup tile
-        small_stage = on && (tiles < mrf_min_tiles() || (mtl == 1 && (Lo & 3)));
-      }
-      // fp16 mode: the chains always run on the stream plan below, one conv_f16.hip launch per convolution
-      if (use_streams && !small_stage && precision == SVOC_PREC_F32 && mrf_grouped(i, cho)) {
-        // MRF with the chains' step-i convolutions grouped into single launches (conv_group_kernel)
-        SVOC_TRY(run_mrf_grouped(st, i, X, XS, bufs, bs, ldo, cho, B, Lo));
-        r ^= 1;
-        ch = cho; L = Lo; ld = ldo;
-        continue;
-      }
-      if (use_streams) SVOC_HIP(hipEventRecord(ev_fork, st));
-      for (int j = 0; j < cfg.n_kernels; ++j) {   // MRF: xs = sum_j ResBlock_j(x); x = xs / n (models.py:149-155)
-        ResSink sink{XS, bs, ldo, 0u, 1.0f};
-        if (j > 0) sink.flags |= F_ACC;
-        if (j == cfg.n_kernels - 1) { sink.flags |= F_DIV; sink.div = (float)cfg.n_kernels; }
-        if (use_streams) {
-          SVOC_HIP(hipStreamWaitEvent(chain_st[j], ev_fork, 0));
-          SVOC_TRY(rbs[i * cfg.n_kernels + j]->run(chain_st[j], X, bs, ldo, nullptr, 0, bufs[3 + 2 * j], bufs[4 + 2 * j], bs, ldo, sink, B, Lo,
-                                                   j > 0 ? chain_done[j - 1] : nullptr, chain_done[j]));
-        } else {
-          SVOC_TRY(rbs[i * cfg.n_kernels + j]->run(st, X, bs, ldo, nullptr, 0, bufs[(r + 3) & 3], R, bs, ldo, sink, B, Lo));
-        }
-      }
-      if (use_streams) { SVOC_HIP(hipStreamWaitEvent(st, chain_done[cfg.n_kernels - 1], 0)); r ^= 1; }
+      SVOC_TRY(run_stage(st, i, R, (long long)ch * ld, ld, X, XS, bufs[(r + 3) & 3], R, bufs, B, L));
+      if (use_streams) r ^= 1;
       else r = (r + 2) & 3;
-      ch = cho; L = Lo; ld = ldo;
+      ch /= 2; L *= u; ld = stage_ld(L);
     }
     last = LastStage{bufs[r], ch, L, ld};
     return out ? post(st, last, out, B) : SVOC_OK;
@@ -1304,6 +1320,79 @@ struct svoc_generator : svoc::HandleDevice { Generator m; };
 struct svoc_synth : svoc::HandleDevice { Synth m; };
 struct svoc_posterior : svoc::HandleDevice { Posterior m; };
 struct svoc_mel_encoder : svoc::HandleDevice { Posterior m; };
+
+// ---- the stages of infer one at a time (svoc_internal.h stage_ops; the stateful stream of stream.hip)
+namespace svoc {
+namespace stage_ops {
+int config(svoc_synth* h, svoc_synth_config* cfg) { *cfg = h->m.cfg; return SVOC_OK; }
+int reserve(svoc_synth* h, int B, int T) {
+  Synth& s = h->m;
+  SVOC_TRY(s.enc.reserve(B, T, 0));
+  SVOC_TRY(s.flow.reserve(B, T, 0, 1));
+  return s.dec.reserve(B, T);
+}
+int set_precision(svoc_synth* h, int mode) { return h->m.dec.set_precision(mode, nullptr); }
+int encoder(svoc_synth* h, hipStream_t st, const float* mel, int mel_ld, const float* eps, int eps_ld, float noise, const float* mask,
+            long long mask_bs, float* xe, float* eo, float* m, float* logs, float* zp, int B, int L) {
+  Synth& s = h->m;
+  const int H = s.cfg.hidden_channels, IC = s.cfg.inter_channels, Tp = pad4(L);
+  const long long hper = (long long)H * Tp, iper = (long long)IC * Tp;
+  {   // pre_enc 1x1 * x_mask (models.py:38-42)
+    ConvArgs a = mk_args();
+    set_in(a, mel, (long long)s.cfg.n_mel * mel_ld, mel_ld, L);
+    a.Ncols = L; a.mask = mask; a.mask_bs = mask_bs;
+    set_out(a.out[0], xe, hper, Tp, H, F_OUTMASK);
+    SVOC_TRY(launch_conv(s.pre_enc, a, B, st));
+  }
+  SVOC_TRY(s.enc.forward(st, xe, hper, Tp, mask, mask_bs, nullptr, 0, eo, hper, Tp, B, L));
+  {   // proj -> z_p = m_p + eps * exp(logs_p) * noise_scale (models.py:44-46, 336)
+    ConvArgs a = mk_args();
+    set_in(a, eo, hper, Tp, L);
+    a.Ncols = L; a.mask = mask; a.mask_bs = mask_bs;
+    a.mode = EPI_PROJ;
+    set_out(a.out[0], m, iper, Tp, IC);
+    a.y2 = logs; a.y3 = zp;
+    a.eps = eps; a.eps_bs = (long long)IC * eps_ld; a.eps_ld = eps_ld; a.noise_scale = noise;
+    SVOC_TRY(launch_conv(s.proj, a, B, st));
+  }
+  return SVOC_OK;
+}
+int coupling(svoc_synth* h, hipStream_t st, int j, const float* x, int x_ld, float* y, int y_ld, const float* mask, long long mask_bs, int B, int L) {
+  Flow& f = h->m.flow;
+  if (j < 0 || j >= f.NF) SVOC_FAIL(SVOC_ERR_INVALID_ARG, "stream: coupling %d of %d", j, f.NF);
+  Coupling& c = *f.rev_p[f.NF - 1 - j];
+  SVOC_TRY(c.run(st, x, (long long)c.C * x_ld, x_ld, y, (long long)c.C * y_ld, y_ld, mask, mask_bs, nullptr, 0, 1, nullptr, B, L));
+  return c.flipped ? 0 : c.half;
+}
+int conv_pre(svoc_synth* h, hipStream_t st, const float* x, int x_ld, float* y, int y_ld, int B, int L) {
+  Generator& g = h->m.dec;
+  return g.run_pre(st, x, (long long)g.cfg.initial_channel * x_ld, x_ld, nullptr, 0, nullptr, y, (long long)g.cfg.upsample_initial_channel * y_ld,
+                   y_ld, B, L);
+}
+int dec_stage(svoc_synth* h, hipStream_t st, int i, const float* x, int x_ld, int B, int L, int T, const float** y, int* y_ld) {
+  Generator& g = h->m.dec;
+  int ch = g.cfg.upsample_initial_channel;
+  long long rate = 1;
+  for (int q = 0; q < i; ++q) { ch /= 2; rate *= g.cfg.upsample_rates[q]; }
+  if (L <= 0 || L > T * rate || g.ws.bytes < g.workspace_bytes(B, T)) SVOC_FAIL(SVOC_ERR_SHAPE, "stream: decoder stage %d window of %d columns beyond its reserve", i, L);
+  const size_t sf = g.stage_floats(T);
+  const int nb = g.n_bufs();
+  std::vector<float*> bufs(nb);
+  for (int q = 0; q < nb; ++q) bufs[q] = g.ws.f() + (size_t)q * sf * B;
+  // the window's input is the stream's own buffer: X, XS and (single-chain plan) the ResBlock scratch all come from the workspace
+  float* X = bufs[1];
+  float* XS = bufs[g.use_streams ? 0 : 2];
+  SVOC_TRY(g.run_stage(st, i, x, (long long)ch * x_ld, x_ld, X, XS, bufs[3], bufs[g.use_streams ? 2 : 0], bufs, B, L));
+  *y = XS;
+  *y_ld = stage_ld(L * g.cfg.upsample_rates[i]);
+  return SVOC_OK;
+}
+int post(svoc_synth* h, hipStream_t st, const float* x, int x_ld, int B, int L, int c0, int n, float* out, long long out_bs) {
+  Generator& g = h->m.dec;
+  return k_conv_post_tanh_range(st, x, (long long)g.post_C * x_ld, x_ld, g.conv_post_w.f(), g.post_C, 7, 0.01f, out, out_bs, B, L, c0, n);
+}
+}  // namespace stage_ops
+}  // namespace svoc
 
 #define SVOC_GUARD_BEGIN try {
 #define SVOC_GUARD_END } catch (const std::exception& e) { ::svoc::set_error("exception: %s", e.what()); return SVOC_ERR_NOMEM; }

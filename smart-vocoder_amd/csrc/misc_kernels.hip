@@ -303,10 +303,11 @@ int k_gate(hipStream_t st, const float* a, const float* b, float* y, int B, int 
 }
 
 // ------------------------------------------------------------------ lrelu -> conv_post (C->1, k taps, no bias) -> tanh
-// (models.py:156-158).  One output row per utterance; every thread produces 4 consecutive samples.
+// (models.py:156-158).  One output row per utterance; every thread produces 4 consecutive samples.  Only the samples [c0, c0 + n) of
+// the L computed are stored, at y[b * y_bs + t - c0] (the stateful stream keeps the interior of a window; infer: c0 = 0, n = L).
 template <int K>
 __global__ void conv_post_tanh_kernel(const float* __restrict__ x, long long x_bs, int x_ld, const float* __restrict__ w,
-                                      int C, float slope, float* __restrict__ y, int L, int vec) {
+                                      int C, float slope, float* __restrict__ y, long long y_bs, int L, int c0, int n, int vec) {
   extern __shared__ float ws[];   // [C][K]
   for (int i = threadIdx.x; i < C * K; i += blockDim.x) ws[i] = w[i];
   __syncthreads();
@@ -314,8 +315,8 @@ __global__ void conv_post_tanh_kernel(const float* __restrict__ x, long long x_b
   constexpr int LEAD = (P + 3) / 4 * 4;           // staging starts at t0 - LEAD
   constexpr int NV = (LEAD + 3 + P) / 4 + 1;      // float4 groups covering [t0-LEAD, t0+3+P]
   const int b = blockIdx.y;
-  const int t0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (t0 >= L) return;
+  const int t0 = (c0 & ~3) + (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  if (t0 >= c0 + n) return;
   const float* xb = x + (long long)b * x_bs;
   float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
   for (int c = 0; c < C; ++c) {
@@ -344,19 +345,20 @@ __global__ void conv_post_tanh_kernel(const float* __restrict__ x, long long x_b
       acc3 = fmaf(wj, v[LEAD - P + j + 3], acc3);
     }
   }
-  float* yb = y + (long long)b * L;
-  if (t0 < L) yb[t0] = tanhf(acc0);
-  if (t0 + 1 < L) yb[t0 + 1] = tanhf(acc1);
-  if (t0 + 2 < L) yb[t0 + 2] = tanhf(acc2);
-  if (t0 + 3 < L) yb[t0 + 3] = tanhf(acc3);
+  float* yb = y + (long long)b * y_bs - c0;
+  const int e = c0 + n;
+  if (t0 >= c0 && t0 < e) yb[t0] = tanhf(acc0);
+  if (t0 + 1 >= c0 && t0 + 1 < e) yb[t0 + 1] = tanhf(acc1);
+  if (t0 + 2 >= c0 && t0 + 2 < e) yb[t0 + 2] = tanhf(acc2);
+  if (t0 + 3 >= c0 && t0 + 3 < e) yb[t0 + 3] = tanhf(acc3);
 }
 
 __global__ void conv_post_tanh_generic_kernel(const float* __restrict__ x, long long x_bs, int x_ld,
                                               const float* __restrict__ w, int C, int K, float slope,
-                                              float* __restrict__ y, int L) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+                                              float* __restrict__ y, long long y_bs, int L, int c0, int n) {
+  const int t = c0 + blockIdx.x * blockDim.x + threadIdx.x;
   const int b = blockIdx.y;
-  if (t >= L) return;
+  if (t >= c0 + n) return;
   const int P = (K - 1) / 2;
   const float* xb = x + (long long)b * x_bs;
   float acc = 0.f;
@@ -369,20 +371,25 @@ __global__ void conv_post_tanh_generic_kernel(const float* __restrict__ x, long 
         acc = fmaf(w[c * K + j], v, acc);
       }
     }
-  y[(long long)b * L + t] = tanhf(acc);
+  y[(long long)b * y_bs + t - c0] = tanhf(acc);
 }
 
 int k_conv_post_tanh(hipStream_t st, const float* x, long long x_bs, int x_ld, const float* w, int C, int K, float slope,
                      float* y, int B, int L) {
-  if (B <= 0 || L <= 0) return SVOC_OK;
+  return k_conv_post_tanh_range(st, x, x_bs, x_ld, w, C, K, slope, y, L, B, L, 0, L);
+}
+int k_conv_post_tanh_range(hipStream_t st, const float* x, long long x_bs, int x_ld, const float* w, int C, int K, float slope,
+                           float* y, long long y_bs, int B, int L, int c0, int n) {
+  if (B <= 0 || L <= 0 || n <= 0) return SVOC_OK;
+  if (c0 < 0 || c0 + n > L) SVOC_FAIL(SVOC_ERR_INVALID_ARG, "conv_post: samples [%d, %d) outside the window of %d", c0, c0 + n, L);
   if (K == 7 && C * K * 4 <= 48 * 1024) {
     const int vec = ((reinterpret_cast<uintptr_t>(x) & 15) == 0 && (x_ld & 3) == 0 && (x_bs & 3) == 0) ? 1 : 0;
-    const int nthr = (L + 3) / 4;
+    const int nthr = (c0 + n - (c0 & ~3) + 3) / 4;
     hipLaunchKernelGGL(conv_post_tanh_kernel<7>, dim3((nthr + 255) / 256, B), dim3(256), (size_t)C * K * sizeof(float), st,
-                       x, x_bs, x_ld, w, C, slope, y, L, vec);
+                       x, x_bs, x_ld, w, C, slope, y, y_bs, L, c0, n, vec);
   } else {
-    hipLaunchKernelGGL(conv_post_tanh_generic_kernel, dim3((L + 255) / 256, B), dim3(256), 0, st, x, x_bs, x_ld, w, C, K,
-                       slope, y, L);
+    hipLaunchKernelGGL(conv_post_tanh_generic_kernel, dim3((n + 255) / 256, B), dim3(256), 0, st, x, x_bs, x_ld, w, C, K,
+                       slope, y, y_bs, L, c0, n);
   }
   SVOC_HIP(hipGetLastError());
   stats_add_other();

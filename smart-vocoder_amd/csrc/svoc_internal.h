@@ -296,6 +296,9 @@ int k_sequence_mask(hipStream_t st, const int64_t* lengths, float* mask, int B, 
 int k_gate(hipStream_t st, const float* a, const float* b, float* y, int B, int H, int T);
 int k_conv_post_tanh(hipStream_t st, const float* x, long long x_bs, int x_ld, const float* w, int C, int K, float slope,
                      float* y, int B, int L);
+// the same over a window of L columns, storing only samples [c0, c0 + n) at y[b * y_bs + t - c0] (the stateful stream's tail)
+int k_conv_post_tanh_range(hipStream_t st, const float* x, long long x_bs, int x_ld, const float* w, int C, int K, float slope,
+                           float* y, long long y_bs, int B, int L, int c0, int n);
 struct CopyMany { const float* src[5]; float* dst[5]; long long s_bs[5], d_bs[5]; int s_ld[5], d_ld[5], rows[5]; int n, cols, B; };
 int k_copy2d_many(hipStream_t st, const CopyMany& m);      // up to five strided copies with one column count in one launch (misc_kernels.hip)
 int k_copy2d(hipStream_t st, const float* src, long long s_bs, int s_ld, float* dst, long long d_bs, int d_ld, int B,
@@ -304,6 +307,27 @@ int k_flip_copy(hipStream_t st, const float* src, long long s_bs, int s_ld, floa
                 int C, int T);
 int k_fill(hipStream_t st, float* p, size_t n, float v);
 int k_frame_blocks(hipStream_t st, const float* y, int B, int Lw, int pad, int pad2, int hop, float* xt, long long xt_bs, int xt_ld, int nblocks);
+
+// engine.hip: the stages of SynthesizerTrn.infer one at a time over a window of columns, for the stateful stream (stream.hip).  They issue the
+// launches infer issues for those stages, on the handle's weights and module workspaces; tensors are [B][C][ld] with batch stride C * ld.
+namespace stage_ops {
+int config(svoc_synth* h, svoc_synth_config* cfg);
+int reserve(svoc_synth* h, int B, int T);         // module workspaces for windows of up to T frames (may block; create time only)
+int set_precision(svoc_synth* h, int mode);       // the decoder's precision switch; returns the previous mode
+// mel encoder + reparameterisation (pre_enc -> WN -> proj with EPI_PROJ) over L frames with the all-ones `mask` (row stride mask_bs):
+// z_p [B][IC][ld] (ld = pad4(L)); xe, eo [B][H][ld], m, logs [B][IC][ld] are scratch
+int encoder(svoc_synth* h, hipStream_t st, const float* mel, int mel_ld, const float* eps, int eps_ld, float noise, const float* mask,
+            long long mask_bs, float* xe, float* eo, float* m, float* logs, float* zp, int B, int L);
+// the j-th reverse coupling in run order (flow.rev_p[NF - 1 - j]): writes the x1 row block of y [B][IC][y_ld]; returns its first row
+// (the x0 block passes through unchanged) or a negative status
+int coupling(svoc_synth* h, hipStream_t st, int j, const float* x, int x_ld, float* y, int y_ld, const float* mask, long long mask_bs, int B, int L);
+int conv_pre(svoc_synth* h, hipStream_t st, const float* x, int x_ld, float* y, int y_ld, int B, int L);
+// upsampler i + MRF over L input columns: the result is left in the decoder's workspace (*y, row stride *y_ld, batch stride C * *y_ld);
+// the workspace must have been reserved for T frames and L <= T * rate(input of stage i)
+int dec_stage(svoc_synth* h, hipStream_t st, int i, const float* x, int x_ld, int B, int L, int T, const float** y, int* y_ld);
+// lrelu -> conv_post -> tanh over L columns; samples [c0, c0 + n) to out[b * out_bs + t - c0]
+int post(svoc_synth* h, hipStream_t st, const float* x, int x_ld, int B, int L, int c0, int n, float* out, long long out_bs);
+}
 
 // stats / profiler
 bool prof_enabled();

@@ -320,7 +320,7 @@ class SynthesizerTrn(_HipModule):
         N.require_gpu(p)
         return p.device
 
-    def _create(self, h, tab):
+    def _synth_config(self):
         c = N.svoc_synth_config()
         c.n_mel = 80
         c.inter_channels = self.inter_channels
@@ -329,7 +329,18 @@ class SynthesizerTrn(_HipModule):
         c.flow_n_layers, c.flow_kernel_size, c.flow_dilation_rate, c.flow_n_flows = 8, 5, 1, 4
         c.gin_channels = self.gin_channels
         c.dec = self.dec._config()
+        return c
+
+    def _create(self, h, tab):
+        c = self._synth_config()
         N.check(N.lib().svoc_synth_create(h.out(), c, tab.arr, tab.n))
+
+    def stream_geometry(self):
+        """Extension: the stage geometry of the stateful stream (svoc_stream_geometry; host only, no device needed) -
+        ``{"stages": [{"name", "u", "rate", "h_left", "h_right"}, ...], "lookahead_frames", "hop"}``.  Output column n of a stage
+        depends on exactly its input columns m with ``n - h_left <= m * u <= n + h_right``; ``rate`` is the stage's output columns
+        per mel frame."""
+        return stream_geometry(self._synth_config())
 
     def forward(self, x, x_lengths, y, y_lengths, sid=None):
         raise NotImplementedError("training forward is outside the MI355X inference path; use infer()")
@@ -432,10 +443,22 @@ class SynthesizerTrn(_HipModule):
             out[:, :, s * hop:e * hop] = o[:, :, (s - a) * hop:(e - a) * hop]
         return out
 
-    def stream(self, noise_scale=1, halo_frames=None, *, decoder_precision="fp32"):
+    def stream(self, noise_scale=1, halo_frames=None, *, decoder_precision="fp32", carry_state=False, max_chunk_frames=None):
         """Incremental long-form inference: ``s = net.stream(noise_scale=.667)``, then ``wave = s.push(mel_chunk)``
         as mel frames arrive and ``wave = s.flush()`` at the end; the concatenated pieces equal one ``infer`` over the whole
-        utterance (to fp32 summation order, as ``infer_chunked``).  See :class:`InferStream`."""
+        utterance (to fp32 summation order, as ``infer_chunked``).  See :class:`InferStream`.
+
+        ``carry_state=True`` (extension, keyword only) returns a :class:`StatefulStream` instead: the same contract, run natively
+        stage by stage with each stage's state carried between pushes (no re-run of the halo through the whole path), releasing
+        samples after ``lookahead_frames`` of look-ahead.  It takes ``max_chunk_frames`` (default 512: the largest push run in one
+        piece; larger pushes are split) and no ``halo_frames``."""
+        if carry_state:
+            if halo_frames is not None:
+                raise ValueError("halo_frames does not apply to carry_state=True: every stage carries exactly its own halo")
+            return StatefulStream(self, noise_scale=noise_scale, decoder_precision=decoder_precision,
+                                  max_chunk_frames=512 if max_chunk_frames is None else max_chunk_frames)
+        if max_chunk_frames is not None:
+            raise ValueError("max_chunk_frames applies to carry_state=True only")
         return InferStream(self, noise_scale=noise_scale, halo_frames=halo_frames, decoder_precision=decoder_precision)
 
     def voice_conversion(self, y, y_lengths, sid_src, sid_tgt, eps=None):
@@ -520,3 +543,139 @@ class InferStream:
         self.mel = self.eps = None
         self.start = self.emitted
         return out
+
+
+def stream_geometry(cfg):
+    """The stateful stream's stage geometry for a svoc_synth_config (see SynthesizerTrn.stream_geometry); host only."""
+    lib = N.lib()
+    n = lib.svoc_stream_geometry(cfg, None, 0)
+    N.check(min(n, 0))
+    buf = (N.C.c_int * n)()
+    N.check(min(lib.svoc_stream_geometry(cfg, buf, n), 0))
+    S, la, hop = buf[0], buf[1], buf[2]
+    names = (["encoder"] + [f"coupling.{j}" for j in range(cfg.flow_n_flows)] + ["conv_pre"] +
+             [f"ups.{i}" for i in range(cfg.dec.n_upsamples)] + ["conv_post"])
+    assert len(names) == S, (names, S)
+    stages = [dict(name=names[s], u=buf[3 + 4 * s], rate=buf[4 + 4 * s], h_left=buf[5 + 4 * s], h_right=buf[6 + 4 * s])
+              for s in range(S)]
+    return dict(stages=stages, lookahead_frames=la, hop=hop)
+
+
+class StatefulStream:
+    """Native stateful front of ``SynthesizerTrn.infer`` (``net.stream(carry_state=True)``; include/svoc.h svoc_stream_*): the same
+    ``push`` / ``flush`` contract as :class:`InferStream`, but the library cuts the path into its stages and keeps, at every stage
+    boundary, only the columns the next stage still needs.  A push runs each stage over its new columns plus that stage's own halo, so
+    the work per frame stays close to one-shot ``infer``'s, and the samples of a frame are released once ``lookahead_frames`` more
+    frames have been pushed (InferStream: ``RECEPTIVE_FRAMES``).  Pieces are whole frames; the batch is fixed by the first push, every
+    utterance of it advances in lock step with all frames valid.  ``flush`` ends the utterance (the true end is zero-padded by the
+    convolutions exactly as in one call) and the next push starts a new one.
+
+    The stream uses the net's native handle: ``infer`` calls and other streams of the same net may be interleaved with its pushes (one
+    at a time on a stream).  When the handle is rebuilt (weights changed, ``.to()``) the stream cannot go on: ``push`` / ``flush`` raise."""
+
+    def __init__(self, net, noise_scale=1, *, decoder_precision="fp32", max_chunk_frames=512):
+        self._mode = _decoder_precision(decoder_precision)
+        self.decoder_precision = decoder_precision
+        if int(max_chunk_frames) <= 0:
+            raise ValueError(f"max_chunk_frames must be positive, got {max_chunk_frames}")
+        self.max_chunk_frames = int(max_chunk_frames)
+        self.net = net
+        self.noise_scale = float(noise_scale)
+        self.geometry = net.stream_geometry()
+        self.lookahead_frames = self.geometry["lookahead_frames"]
+        self.hop = self.geometry["hop"]
+        self._ns = None          # N.Handle of the native stream (created by the first push)
+        self._nh = None          # the net's Handle object it was created from
+        self._hval = None
+        self._B = None
+        self._dev = None
+        self._end = 0
+
+    @property
+    def end(self):
+        """frames pushed so far (over every utterance of the stream)"""
+        return self._end
+
+    def _handle(self):
+        """the net's native handle, checked to be the one this stream was created on"""
+        net = self.net
+        if self._nh is None:
+            return net._native()
+        nh = net.__dict__.get("_nh")
+        if nh is not self._nh or not nh.h.value or nh.h.value != self._hval or net.__dict__.get("_nh_sig") != net._sig():
+            raise RuntimeError("the net's native handle was rebuilt (weights changed or moved) after this stream was created; "
+                               "start a new stream")
+        return nh.h
+
+    def _check(self, mel, eps):
+        if not isinstance(mel, torch.Tensor) or mel.dim() != 3 or mel.shape[1] != 80:
+            raise ValueError(f"expected mel [B, 80, t], got {tuple(mel.shape) if isinstance(mel, torch.Tensor) else type(mel)}")
+        if mel.shape[2] < 1 or mel.shape[0] < 1:
+            raise ValueError("a push needs at least one frame of at least one utterance")
+        if not mel.is_cuda:
+            raise ValueError(f"mel must be on the net's device, got {mel.device}")
+        dev = self.net._dev()
+        if mel.device != dev:
+            raise ValueError(f"mel is on {mel.device}, the net on {dev}")
+        if self._B is not None and mel.shape[0] != self._B:
+            raise ValueError("the batch size of a stream is fixed by its first chunk")
+        if eps is not None:
+            if not isinstance(eps, torch.Tensor) or tuple(eps.shape) != (mel.shape[0], self.net.inter_channels, mel.shape[2]):
+                raise ValueError(f"eps must be [B, inter_channels, t] = {(mel.shape[0], self.net.inter_channels, mel.shape[2])}")
+            if eps.device != mel.device:
+                raise ValueError(f"eps is on {eps.device}, mel on {mel.device}")
+        return dev
+
+    def push(self, mel, eps=None):
+        """mel [B, 80, t] (t >= 1 new frames), eps [B, inter_channels, t] or None (drawn) -> waveform [B, 1, n * hop], n >= 0"""
+        dev = self._check(mel, eps)
+        B, _, t = mel.shape
+        with torch.cuda.device(dev):
+            h = self._handle()
+            lib = N.lib()
+            if self._ns is None:
+                ns = N.Handle("svoc_stream_destroy")
+                N.check(lib.svoc_stream_create(ns.out(), h, B, self.max_chunk_frames))
+                self._ns, self._nh, self._hval, self._B, self._dev = ns, self.net._nh, self.net._nh.h.value, B, dev
+            mel = N.f32(mel)
+            if eps is None:
+                eps = torch.randn(B, self.net.inter_channels, t, dtype=torch.float32, device=dev)
+            eps = N.f32(eps)
+            n = N._L(0)
+            N.check(lib.svoc_stream_samples(self._ns.h, t, 0, N.C.byref(n)))
+            out = torch.empty(B, 1, n.value, dtype=torch.float32, device=dev)
+            _set_decoder_precision(self.net, h, lib.svoc_synth_set_decoder_precision, self._mode)
+            w = N._L(0)
+            N.check(lib.svoc_stream_push(self._ns.h, N.stream_ptr(dev), N.ptr(mel), N.ptr(eps), t, self.noise_scale,
+                                         N.ptr(out) if n.value else None, n.value, N.C.byref(w)))
+            assert w.value == n.value, (w.value, n.value)
+        self._end += t
+        return out
+
+    def flush(self):
+        """the samples of the frames still held back; the stream is empty afterwards"""
+        if self._ns is None:
+            return torch.empty(0, 1, 0, dtype=torch.float32, device=self.net._dev())
+        with torch.cuda.device(self._dev):
+            h = self._handle()
+            lib = N.lib()
+            n = N._L(0)
+            N.check(lib.svoc_stream_samples(self._ns.h, 0, 1, N.C.byref(n)))
+            out = torch.empty(self._B, 1, n.value, dtype=torch.float32, device=self._dev)
+            _set_decoder_precision(self.net, h, lib.svoc_synth_set_decoder_precision, self._mode)
+            w = N._L(0)
+            N.check(lib.svoc_stream_flush(self._ns.h, N.stream_ptr(self._dev), self.noise_scale, N.ptr(out) if n.value else None,
+                                          n.value, N.C.byref(w)))
+            assert w.value == n.value, (w.value, n.value)
+        return out
+
+    def stats(self):
+        """{"columns": {stage name: input columns processed so far (windows included)}, "state_bytes": device memory the stream owns}"""
+        names = [s["name"] for s in self.geometry["stages"]]
+        if self._ns is None:
+            return dict(columns={k: 0 for k in names}, state_bytes=0)
+        S = len(names)
+        cols = (N._L * S)()
+        sb = N._L(0)
+        N.check(min(N.lib().svoc_stream_stats(self._ns.h, cols, S, N.C.byref(sb)), 0))
+        return dict(columns={k: int(cols[i]) for i, k in enumerate(names)}, state_bytes=int(sb.value))
